@@ -2,7 +2,7 @@
 """bench.py - scenes/sec of PaSCo MIMO-3 inference on the synthetic 256x256x32 (~10 % occupancy)
 scene S10 (BASELINE.json metric / SURVEY.md 8(d)).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one scene through the hot path: point-feature MLP + voxel max (CylinderFeat), MIMO
 input merge, sparse U-Net encoder / dense bottleneck / generative decoder, the mask-transformer
@@ -19,10 +19,13 @@ itself under `torch.distributed.run`; under a launcher it reads RANK / LOCAL_RAN
                        only its own subnet heads; one RCCL all-gather of per-voxel logits; strong scaling
 Time = max over ranks between two barrier + device-sync fences.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (dominant convolution kernel,
-measured live with HIP events on the launch stream, per layer class with both roofs), `cpu_baseline` (the CPU
-oracle running the same graph on the host cores - the ONLY place the oracle is used here) and `configs` (short
-driver-timed rows of BASELINE.json's other single-GPU configurations).
+A plain run sets up, warms up, times K steps and prints ONE JSON line (rank 0) with the driver's contract fields.
+`--dump-outputs DIR` also writes what the last timed step returned (`dump_outputs`).  `--full` measures the rest after
+the timed steps: `roofline` (dominant convolution kernel, measured live with HIP events on the launch stream, per layer
+class with both roofs), the same loop one scene at a time, with `panoptic_inference`, with the garbage collector on and
+on the exact fp32 MFMA, `cpu_baseline` (the CPU oracle running the same graph on the host cores - the ONLY place the
+oracle is used here) and `configs` (short driver-timed rows of BASELINE.json's other single-GPU configurations); all of
+it goes into the line and `bench_detail.json`.
 """
 import argparse
 import glob
@@ -285,21 +288,27 @@ def physical_cores():
 
 def cpu_baseline(n_infers, in_channels, timed=5):
     """The CPU baseline in a FRESH process with the whole host's CPUs: this process (and every thread pool it has started) is
-    pinned to its GPU's socket, which would halve the baseline's cores."""
+    pinned to its GPU's socket, which would halve the baseline's cores.  An OMP_NUM_THREADS set for the run is passed on:
+    it is the number of CPUs the run may use."""
     cmd = [sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--n-infers", str(n_infers), "--in-channels",
            str(in_channels), "--cpu-baseline-scenes", str(timed)]
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "OMP_NUM_THREADS")}
-    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1800)
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=CPU_BASELINE_BUDGET_S + 240)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if out.returncode != 0 or not lines:
         raise RuntimeError(f"cpu baseline process failed ({out.returncode}): {out.stderr[-400:]}")
     return json.loads(lines[-1])
 
 
+CPU_BASELINE_BUDGET_S = 240     # the CPU baseline times no further scene after this many seconds (at least one is timed)
+
+
 def cpu_baseline_here(n_infers, in_channels, timed=5):
     """Same graph, oracle backend (C + OpenMP) + torch CPU for the dense parts, host cores only: ONE warm-up scene on the
     same 256x256x32 grid (thread pools, page faults, weight operand caches), then `timed` full S10 scenes (seeds 0 .. timed - 1),
-    median reported (one warm-up + 5 timed scenes, median; ~23 s per scene on the 128-core host)."""
+    median reported (one warm-up + 5 timed scenes, median; ~23 s per scene on the 128-core host).  Threads:
+    OMP_NUM_THREADS where it is set, else the physical cores; a host with few CPUs times fewer scenes
+    (CPU_BASELINE_BUDGET_S), so that `--full` ends in bounded time."""
     from oracle.build import build_oracle
     from pasco_amd.me import backend
     from pasco_amd.me.backend import CBackend
@@ -309,14 +318,18 @@ def cpu_baseline_here(n_infers, in_channels, timed=5):
             os.sched_setaffinity(0, range(os.cpu_count() or 1))
         except OSError:
             pass
-    cores = physical_cores()
+    given = os.environ.get("OMP_NUM_THREADS", "")
+    cores = int(given) if given.isdigit() and int(given) > 0 else physical_cores()
     torch.set_num_threads(cores)
     os.environ["OMP_NUM_THREADS"] = str(cores)     # the oracle's OpenMP runtime starts with its first call, below
     backend.register_checker_backend(CBackend(build_oracle(), "pho_", "cpu"))
     try:
         net = build_net(n_infers, in_channels, "cpu")
         times, occ = [], 0
+        start = time.time()
         for k in range(timed + 1):                 # scene 0 twice: once as the warm-up, once timed
+            if times and time.time() - start > CPU_BASELINE_BUDGET_S:
+                break
             full = make_scene(max(k - 1, 0), n_infers=n_infers, in_channels=in_channels)
             tk = TeacherKeep(full, "cpu")
             with torch.no_grad():
@@ -330,9 +343,10 @@ def cpu_baseline_here(n_infers, in_channels, timed=5):
         times.sort()
         med = times[len(times) // 2]
         return dict(value=round(1.0 / med, 5), unit="scenes/s", cores=cores, kind="port",
-                    sample=f"median of {timed} full S10 scenes (seeds 0..{timed - 1}, M={n_infers}, {occ} occupied voxels in seed 0; "
+                    sample=f"median of {len(times)} full S10 scenes (seeds 0..{len(times) - 1}, M={n_infers}, {occ} occupied voxels in seed 0; "
                            f"{', '.join(f'{t:.2f}' for t in times)} s) after one warm-up scene on the same grid; oracle C/OpenMP "
-                           f"sparse ops + torch-CPU dense ops; {cpu_model()}: {cores} threads = physical cores of "
+                           f"sparse ops + torch-CPU dense ops; {cpu_model()}: {cores} threads = "
+                           f"{'OMP_NUM_THREADS' if given == str(cores) else 'physical cores'} of "
                            f"{os.cpu_count()} logical CPUs (OpenMP and torch)")
     finally:
         backend.register_checker_backend(None)
@@ -419,6 +433,76 @@ def compact_line(res, detail_path=None):
     if len(json.dumps(line)) > LINE_LIMIT and "roofline" in line:
         line["roofline"].pop("classes", None)
     return line
+
+
+# ------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ------------------------------------------------------------------------------------------------------
+DUMP_LIMIT = 64 << 20           # bytes of all dumped arrays together
+DUMP_ARRAY_BYTES = 512 << 10    # a larger array is written as a fixed, seeded sample of its rows
+
+
+def output_leaves(obj, name):
+    """(name, tensor) for every dense tensor and (name, (C, F)) for every sparse tensor inside nested dicts / lists."""
+    from pasco_amd.me import SparseTensor
+    if isinstance(obj, SparseTensor):
+        yield name, (obj.C, obj.F)
+    elif isinstance(obj, torch.Tensor):
+        yield name, obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            yield from output_leaves(v, f"{name}.{k}")
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            yield from output_leaves(v, f"{name}.{i}")
+
+
+def _host_array(t):
+    """float32 for floating point of 32 bits or fewer, float64 for float64 and for integers / booleans (exact)."""
+    import numpy as np
+    a = t.detach().cpu()
+    if a.is_floating_point():
+        return a.double().numpy() if a.dtype == torch.float64 else a.float().numpy()
+    return a.numpy().astype(np.float64)
+
+
+def dump_outputs(outputs, directory):
+    """Write every array of `outputs` (one step's return values) as <directory>/<name>.npy.  A sparse tensor becomes
+    <name>.C (coordinates) and <name>.F (features) with its rows in lexicographic coordinate order, so that two builds that
+    emit the same rows in another order compare equal.  An array above DUMP_ARRAY_BYTES keeps a sample of its rows (of its
+    elements if dense), drawn with a seed fixed by its name; C and F keep the same rows.  Returns {name: shape written}."""
+    import zlib
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = []
+    for name, x in output_leaves(outputs, ""):
+        name = name.lstrip(".")
+        if isinstance(x, tuple):
+            c, f = _host_array(x[0]), _host_array(x[1])
+            order = np.lexsort(c.T[::-1])            # column 0 is the primary key
+            c, f = c[order], f[order]
+            row_bytes = max(f[:1].nbytes, c[:1].nbytes, 1)
+            if max(c.nbytes, f.nbytes) > DUMP_ARRAY_BYTES:
+                rows = np.random.default_rng(zlib.crc32(name.encode())).choice(len(f), DUMP_ARRAY_BYTES // row_bytes,
+                                                                               replace=False)
+                rows.sort()
+                c, f = c[rows], f[rows]
+            arrays += [(name + ".C", c), (name + ".F", f)]
+        else:
+            a = _host_array(x)
+            if a.nbytes > DUMP_ARRAY_BYTES:
+                a = a.reshape(-1)
+                idx = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, DUMP_ARRAY_BYTES // a.itemsize,
+                                                                              replace=False)
+                idx.sort()
+                a = a[idx]
+            arrays.append((name, a))
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_LIMIT:
+        raise RuntimeError(f"--dump-outputs: {total} bytes over the limit of {DUMP_LIMIT}")
+    for name, a in arrays:
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays}
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -531,11 +615,17 @@ def main():
     ap.add_argument("--in-flight", type=int, default=3,
                     help="scenes in flight per GPU: worker threads, each with its own HIP stream, take the steps from a shared "
                          "counter (a step's ~60 host synchronisations then overlap with the other scene's kernels); 1 = one "
-                         "scene at a time, also measured and reported as `in_flight_1`")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip per-launch HIP events")
-    ap.add_argument("--no-exact", action="store_true", help="skip the extra exact-fp32-MFMA timing")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short rows of the other configurations")
+                         "scene at a time, also measured and reported as `in_flight_1` with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, one scene at a time, step_inference, the loop with "
+                         "the garbage collector on, the exact fp32 MFMA, the other configurations and the CPU baseline, "
+                         "and write bench_detail.json")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full without per-launch HIP events")
+    ap.add_argument("--no-exact", action="store_true", help="--full without the extra exact-fp32-MFMA timing")
+    ap.add_argument("--no-configs", action="store_true", help="--full without the short rows of the other configurations")
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-scenes", type=int, default=5, help=argparse.SUPPRESS)
@@ -545,6 +635,8 @@ def main():
     args = ap.parse_args()
     if args.n_infers is None:
         args.n_infers = 8 if args.mode == "subnet-heads" else 3
+    if not args.full:               # a plain run measures the timed steps and nothing else
+        args.no_cpu_baseline = args.no_profile = args.no_exact = args.no_configs = True
 
     if args.cpu_baseline_only:           # child of `cpu_baseline`: nothing but the oracle + torch-CPU graph, all host CPUs
         print(json.dumps(cpu_baseline_here(args.n_infers, args.in_channels, args.cpu_baseline_scenes)), flush=True)
@@ -583,7 +675,10 @@ def main():
     heads = args.mode == "subnet-heads"
     # scenes-mode: rank r owns its own scenes; subnet-heads: every rank works on the SAME scene sequence
     seeds = [(0 if heads else rank * args.scenes) + i for i in range(args.scenes)]
-    scenes = [make_scene(seed=s, n_infers=args.n_infers, in_channels=args.in_channels).to(device) for s in seeds]
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(min(len(seeds), 4)) as ex:        # numpy work, each scene from its own seeded generator
+        scenes = list(ex.map(lambda s: make_scene(seed=s, n_infers=args.n_infers, in_channels=args.in_channels), seeds))
+    scenes = [sc.to(device) for sc in scenes]
     teachers = [TeacherKeep(sc, device) for sc in scenes]
     if not (args.mode == "subnet-heads" and world > 1) and os.environ.get("PASCO_BENCH_TEACHER_LIVE", "0") != "1":
         # scene preparation: the teacher-forced keep's hash lookups are answered once per scene here, outside every timed region
@@ -593,7 +688,8 @@ def main():
         torch.cuda.synchronize()
     step_fn = run_scene_subnet_heads if (heads and world > 1) else (lambda n, s, t, w=None: run_scene(n, s, t, w))
     prof = ConvProfiler()
-    prof.wrap(be)
+    if not args.no_profile:
+        prof.wrap(be)
 
     def barrier():
         if world > 1:
@@ -625,7 +721,9 @@ def main():
         last = {}
 
         def done(i, o):
-            last["out"], last["panop"] = o
+            if i >= last.get("step", i):     # the outputs of the highest step number, whichever stream finished last
+                last["step"] = i
+                last["out"], last["panop"] = o
             if marks is not None:
                 marks.append(time.perf_counter())
 
@@ -658,21 +756,24 @@ def main():
         gc.disable()
     # the write test above walked every cached block and the collector has just run: a last untimed stretch of the loop itself, so that
     # the timed steps start from the state a serving loop is in (one box's first process ran its first 20 timed steps 25 - 45 % slow
-    # right after them: profiles/r4x_bench_full.json)
+    # right after them: profiles/r4x_bench_full.json); its length does not grow with --steps
     if args.in_flight > 1:
-        run_steps(0, max(2 * args.in_flight * len(scenes), args.steps), args.in_flight)
+        run_steps(0, 2 * args.in_flight * len(scenes), args.in_flight)
     alloc_log = {"after_warmup": allocator_state(device)}
     barrier()
     cpu0 = time.process_time()
     t0 = time.perf_counter()
     marks = [t0]
-    last = run_steps(0, args.steps, args.in_flight, window, marks)
+    last = run_steps(0, args.steps, args.in_flight, window if args.full else None, marks)
     barrier()
     elapsed = time.perf_counter() - t0
     host_cpu_s = time.process_time() - cpu0      # CPU seconds of every thread of this process over the timed loop
     alloc_log["after_timed_loop"] = allocator_state(device)
     out, panop = last["out"], last["panop"]
     prof.enabled = False
+    dumped = None
+    if args.dump_outputs and rank == 0:         # before any later pass can reuse a buffer of the last step
+        dumped = dump_outputs({"out": out, "panop": panop}, args.dump_outputs)
     # the timed steps in groups of `in_flight` completions: a box that goes through a slow period (seen in rounds 2 - 3:
     # the HBM-bound launches 6 x slower for ~0.3 s, then normal again) shows here, not only in the mean
     g = max(args.in_flight, 1)
@@ -686,7 +787,7 @@ def main():
         per = [round((b - a) * 1e3, 1) for a, b in zip(marks[:-1], marks[1:])]
         print(f"[bench] per-step host ms: {per}", file=sys.stderr, flush=True)
     one_in_flight = step_inference = None
-    if args.in_flight > 1 and world == 1:          # the same K steps, one scene at a time on one stream (no per-launch events)
+    if args.full and args.in_flight > 1 and world == 1:    # the same K steps, one scene at a time on one stream (no per-launch events)
         run_steps(0, len(scenes), 1)               # untimed: the main stream's pool as the collector-less loop leaves it
         window = []
         mallocs0 = allocator_state(device).get("device_mallocs", 0)
@@ -750,7 +851,7 @@ def main():
 
     single = world == 1
     gc_row = None
-    if single:                    # the same loop with Python's collector running (what an unmanaged serving loop pays)
+    if single and args.full:      # the same loop with Python's collector running (what an unmanaged serving loop pays)
         k3 = max(4, args.steps // 3)
         gc.enable()
         torch.cuda.synchronize()
@@ -898,7 +999,9 @@ def main():
             except Exception as e:  # the baseline must never take the GPU number down with it
                 res["cpu_baseline"] = {"value": None, "unit": "scenes/s", "cores": os.cpu_count(), "kind": "port",
                                        "sample": f"failed: {type(e).__name__}: {e}"}
-        detail = write_detail(res)
+        if dumped is not None:
+            print(f"[bench] step {last['step']}: {len(dumped)} arrays written to {args.dump_outputs}", file=sys.stderr, flush=True)
+        detail = write_detail(res) if args.full else None
         line = compact_line(res, detail)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -100,3 +100,35 @@ def test_window_kernel_headline_sits_under_the_matrix_roof():
     assert r["alg_roof"]["bound"] == "hbm" and r["alg_roof"]["frac"] > 1.0          # the quotient that is not an HBM number
     line = bench.compact_line({"metric": "m", "value": 1.0, "roofline": r, "config": {"workload": "w"}})
     assert line["roofline"]["bound"] == "mfma" and "alg_roof" in line["roofline"]
+
+
+def test_dump_outputs_writes_order_free_bounded_float_arrays(oracle_registered, tmp_path, monkeypatch):
+    """`--dump-outputs`: every array of nested step outputs as <name>.npy in float32 / float64; a sparse tensor's rows in
+    coordinate order (two builds that emit the same rows in another order write the same files); a large array as a fixed,
+    seeded sample of its rows, the same rows of C and F."""
+    import numpy as np
+    import torch
+    from pasco_amd.me import SparseTensor
+    monkeypatch.setattr(bench, "DUMP_ARRAY_BYTES", 4096)
+    g = torch.Generator().manual_seed(0)
+    coords = torch.cat([torch.zeros(300, 1, dtype=torch.int32), torch.randperm(300 * 7, generator=g)[:300, None].int()
+                        .repeat(1, 3) // torch.tensor([1, 7, 49], dtype=torch.int32)], dim=1)
+    feats = torch.randn(300, 8, generator=g)
+    perm = torch.randperm(300, generator=g)
+    dense = torch.randn(1, 12, 21, generator=g)
+
+    def outputs(p):
+        return {"out": {"logits": [SparseTensor(feats[p], coords[p])], "query": dense},
+                "panop": [{"n": 3, "mask": torch.arange(2000) % 3 == 0}]}
+
+    a = bench.dump_outputs(outputs(torch.arange(300)), str(tmp_path / "a"))
+    b = bench.dump_outputs(outputs(perm), str(tmp_path / "b"))
+    assert a == b and set(a) == {"out.logits.0.C", "out.logits.0.F", "out.query", "panop.0.mask"}
+    assert a["out.logits.0.F"] == [4096 // 32, 8] and a["out.query"] == [1, 12, 21] and a["panop.0.mask"] == [4096 // 8]
+    for name in a:
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), name
+    c, f = np.load(tmp_path / "a" / "out.logits.0.C.npy"), np.load(tmp_path / "a" / "out.logits.0.F.npy")
+    assert c.dtype == np.float64 and (np.diff(c[:, 1:] @ np.array([1e6, 1e3, 1.0])) > 0).all()      # sorted, distinct rows
+    row = {tuple(r): i for i, r in enumerate(coords.double().numpy())}
+    assert np.array_equal(f, feats.numpy()[[row[tuple(r)] for r in c]])                         # the same rows of C and F
