@@ -228,6 +228,11 @@ class FrameReader:
                 os.path.join(self.preprocess_root, "waffleiron_v2/sequences", sequence, "seg_feats_tta", f"{frame_id}.pkl"),
                 os.path.join(self.root, "dataset", "sequences", sequence, "labels", f"{frame_id}.label"))
 
+    def labels(self, sequence: str, frame_id: str):
+        """The frame's origin label grids (semantic uint8 with 255 = unknown, instance ids): what the reference's
+        `semantic_label_origin` / `mask_label_origin` are built from; `pasco_amd.eval.GroundTruth.from_labels` takes them."""
+        return read_instance_label_pickle(self.paths(sequence, frame_id)[0])
+
     def batch(self, sequence: str, frame_id: str, Ts: Sequence[torch.Tensor], embedding_index: int = 0) -> Dict:
         lab, feats, pts = self.paths(sequence, frame_id)
         sem, ins = read_instance_label_pickle(lab)

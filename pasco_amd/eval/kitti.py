@@ -1,0 +1,82 @@
+"""Score a trained checkpoint on a SemanticKITTI tree and print the reference's three result tables.
+
+    python -m pasco_amd.eval.kitti --root <kitti root> --preprocess-root <preprocess root> --ckpt <model.ckpt> [--frames N]
+
+Per frame: `FrameReader.batch` -> `net_from_checkpoint(...).step_inference` -> `SceneEvaluator.add` with the frame's
+`GroundTruth`.  Subnet transforms: subnet 0 sees the frame as it is, subnet i >= 1 under the fixed rotation / translation
+table of the synthetic benchmark (theta_i in (0, 10, -10, 20, -20, 30, -30, 5) degrees,
+t_i = ((i mod 3 - 1) 0.2, (floor(i / 3) mod 3 - 1) 0.2, 0) m).  This is NOT the reference's validation draw, which samples a
+random transform per subnet and frame, so subnet rows can differ from the paper's by that draw.  The "inference time" column
+is the measured mean wall time of `step_inference` in milliseconds (the reference prints 0.00 there: its caller passes 0).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import time
+
+import numpy as np
+import torch
+
+from ..data import FrameReader, net_from_checkpoint
+from ..graph.synth import THETAS_DEG, generate_transformation
+from .gt import GroundTruth
+from .metrics import SceneEvaluator
+
+
+def subnet_transforms(m: int):
+    Ts = [torch.eye(4)]
+    for i in range(1, m):
+        t = np.array([((i % 3) - 1) * 0.2, (((i // 3) % 3) - 1) * 0.2, 0.0])
+        Ts.append(torch.from_numpy(generate_transformation(THETAS_DEG[i % len(THETAS_DEG)], t)).float())
+    return Ts
+
+
+def frames_of(preprocess_root: str, sequence: str):
+    d = os.path.join(preprocess_root, "instance_labels_v2", sequence)
+    return sorted(f[:-len("_1_1.pkl")] for f in os.listdir(d) if f.endswith("_1_1.pkl"))
+
+
+def evaluate(root: str, preprocess_root: str, ckpt: str, sequence: str = "08", frames: int = 0, device: str = "cuda"):
+    """-> (SceneEvaluator, mean step time in ms)."""
+    dev = torch.device(device)
+    net = net_from_checkpoint(ckpt, device=dev)
+    reader = FrameReader(root, preprocess_root)
+    ids = frames_of(preprocess_root, sequence)
+    if frames:
+        ids = ids[:frames]
+    if not ids:
+        raise FileNotFoundError(f"no labelled frame of sequence {sequence} under {preprocess_root}")
+    Ts = subnet_transforms(net.n_infers)
+    ev = SceneEvaluator(n_classes=net.n_classes, thing_ids=net.thing_ids, n_outputs=net.n_infers + 1)
+    times = []
+    for fid in ids:
+        sem, ins = reader.labels(sequence, fid)
+        net.ensembler.scene_size = tuple(int(v) for v in sem.shape)
+        b = reader.batch(sequence, fid, Ts)
+        with torch.no_grad():
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            outs, sem_probs, _ = net.step_inference([t.to(dev) for t in b["in_feats"]], [t.to(dev) for t in b["in_coords"]],
+                                                    [t.to(dev) for t in b["Ts"]], b["global_min_Cs"], b["global_max_Cs"],
+                                                    b["min_Cs"], b["max_Cs"])
+            torch.cuda.synchronize(dev)
+            times.append(1e3 * (time.perf_counter() - t0))
+            ev.add(outs, sem_probs, GroundTruth.from_labels(sem, ins, net.thing_ids, device=dev))
+    return ev, float(np.mean(times))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--root", required=True)
+    ap.add_argument("--preprocess-root", required=True)
+    ap.add_argument("--ckpt", required=True)
+    ap.add_argument("--sequence", default="08")
+    ap.add_argument("--frames", type=int, default=0, help="first N labelled frames (0 = all)")
+    a = ap.parse_args(argv)
+    ev, step_ms = evaluate(a.root, a.preprocess_root, a.ckpt, a.sequence, a.frames)
+    print(ev.tables(step_time=step_ms), end="")
+
+
+if __name__ == "__main__":
+    main()

@@ -70,6 +70,14 @@ class PanopticResult(dict):
         self[key] = val
         return val
 
+    def sparse_rows(self):
+        """(coords [N, 4] int32 (batch, x, y, z), scene_size, min_C, panoptic id [N], vox_conf [N]) of a device-path result:
+        the rows its dense maps would be made of, without making them.  None when the result holds no rows."""
+        if self._lazy is None:
+            return None
+        coords, scene_size, min_C, rows, _, _ = self._lazy
+        return coords, scene_size, min_C, rows["panoptic"], rows["vox_conf"]
+
     # the lazy keys behave like the real ones of the dict the reference returns (helper.py:291-303): membership, get, iteration
     def _lazy_keys(self):
         return () if self._lazy is None else tuple(k for k in DENSE_KEYS + ("vox_all_mask_probs_denses",) if not dict.__contains__(self, k))
