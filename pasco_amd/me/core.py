@@ -90,6 +90,15 @@ class _CoordMap:
         return self._tvals
 
 
+def tensor_version(t: torch.Tensor) -> Optional[int]:
+    """`t._version`, or None for an inference tensor (made under torch.inference_mode(): it has no version counter, reading it
+    raises).  Caches keyed on it treat None as "cannot tell whether it changed"."""
+    try:
+        return t._version
+    except RuntimeError:
+        return None
+
+
 def kernel_offsets(kernel_size, tensor_stride, dilation=1, transposed=False) -> List[Tuple[int, int, int]]:
     """Offsets of a hyper-cube kernel in upstream's enumeration: x fastest; odd sizes centred,
     even sizes start at 0.  Scaled by tensor stride * dilation; negated for
@@ -269,13 +278,14 @@ class CoordinateManager:
         # pruning several tensors of one map with the SAME mask tensor (features and their logits) is one map
         # event: the second call reuses the first one's rows and key (the mask tensor is kept alive by the entry)
         last = self.__dict__.get("_last_prune")
-        if last is not None and last[0] == in_key and last[1] is mask and last[2] == mask._version:
+        # (an inference-tensor mask has no version: the same tensor object is then the same event)
+        if last is not None and last[0] == in_key and last[1] is mask and last[2] == tensor_version(mask):
             return last[3], last[4]
         be = self.backend()
         keep = be.mask_compact(mask.contiguous())
         coords = be.gather_rows(m.coords, keep)
         out_key = self.insert_unique(coords, in_key.tensor_stride)
-        self.__dict__["_last_prune"] = (in_key, mask, mask._version, out_key, keep)
+        self.__dict__["_last_prune"] = (in_key, mask, tensor_version(mask), out_key, keep)
         return out_key, keep
 
     def prune_batch(self, jobs):
@@ -287,7 +297,7 @@ class CoordinateManager:
         for in_key, mask in jobs:
             m = self._maps[in_key]
             assert mask.shape[0] == m.n, f"mask has {mask.shape[0]} rows, map has {m.n}"
-            k = (in_key, id(mask), mask._version)
+            k = (in_key, id(mask), tensor_version(mask))
             if k not in uniq:
                 uniq[k] = len(order)
                 order.append((in_key, mask))
@@ -296,7 +306,7 @@ class CoordinateManager:
         for (in_key, mask), keep in zip(order, keeps):
             coords = be.gather_rows(self._maps[in_key].coords, keep)
             done.append((self.insert_unique(coords, in_key.tensor_stride), keep))
-        return [done[uniq[(in_key, id(mask), mask._version)]] for in_key, mask in jobs]
+        return [done[uniq[(in_key, id(mask), tensor_version(mask))]] for in_key, mask in jobs]
 
     def union(self, key_a: CoordinateMapKey, key_b: CoordinateMapKey):
         """-> (out_key, rows_a2out, rows_b2out): lhs rows first, then unseen rhs rows."""

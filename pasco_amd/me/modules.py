@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import backend as B
-from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple
+from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple, tensor_version
 
 
 class MinkowskiModuleBase(nn.Module):
@@ -117,13 +117,14 @@ class _ConvBase(MinkowskiModuleBase):
                 torch.is_grad_enabled() and self.kernel.requires_grad and self.training:
             return be.conv_fwd(feats, kernel, nbr, n_out, bias=bias, **pro)
         w = self.kernel
-        ver = (w._version, w.data_ptr(), w.device)
+        v = tensor_version(w)         # None: a parameter made under torch.inference_mode() - no version counter, split every call
+        ver = None if v is None else (v, w.data_ptr(), w.device)
         hit = self.__dict__.get("_ph_me_split")
-        if hit is None or hit[0] != ver:
+        if ver is None or hit is None or hit[0] != ver:
             hit = (ver, be.split_weight_rows(kernel))
             if w.is_cuda and not torch.cuda.is_current_stream_capturing():
                 torch.cuda.current_stream(w.device).synchronize()     # the cache serves every stream (fused.publish)
-            self.__dict__["_ph_me_split"] = hit
+            self.__dict__["_ph_me_split"] = hit if ver is not None else None
         flag = torch.zeros(1, dtype=torch.int32, device=feats.device)
         xs = be.split_rows(feats, status=flag, **pro)
         win = None
@@ -192,10 +193,10 @@ class MinkowskiBatchNorm(nn.Module):
         m = self.bn
         bufs, pars = m._buffers, m._parameters
         rm, rv, w, b = bufs["running_mean"], bufs["running_var"], pars.get("weight"), pars.get("bias")
-        ver = (rm._version, rv._version, w._version if w is not None else -1, b._version if b is not None else -1, rm.device,
-               rm.data_ptr())
+        vers = [tensor_version(t) if t is not None else -1 for t in (rm, rv, w, b)]
+        ver = None if None in vers else tuple(vers) + (rm.device, rm.data_ptr())    # None: inference tensors, fold every call
         hit = self.__dict__.get("_ph_me_folded")
-        if hit is None or hit[0] != ver:
+        if ver is None or hit is None or hit[0] != ver:
             with torch.no_grad():
                 scale = torch.rsqrt(rv.float() + m.eps) * (w.float() if w is not None else 1.0)
                 shift = (b.float() if b is not None else 0.0) - rm.float() * scale
