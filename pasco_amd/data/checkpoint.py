@@ -48,10 +48,11 @@ def remap_reference_state_dict(sd: Dict[str, torch.Tensor], net) -> "OrderedDict
     return out
 
 
-def net_from_checkpoint(path: str, device="cpu", **overrides):
+def net_from_checkpoint(path: str, device="cpu", thing_ids=None, **overrides):
     """Build `PascoNet` from the checkpoint's hyper-parameters (n_classes, n_infers, in_channels, f, num_queries,
     heavy_decoder, the three thresholds; `overrides` win, as the keyword arguments of `load_from_checkpoint` do) and
-    load the weights strictly."""
+    load the weights strictly.  `thing_ids` are the dataset's instance classes (the reference imports them from its
+    params module, they are not a hyper-parameter): None keeps PascoNet's SemanticKITTI ids, KITTI-360 passes (1..6)."""
     from ..graph import PascoNet
     sd, hp = load_lightning_state_dict(path)
     hp.update(overrides)
@@ -67,6 +68,8 @@ def net_from_checkpoint(path: str, device="cpu", **overrides):
             kw["hidden_dim"] = int(sd[p + "query_feat.weight"].shape[1])
             kw["dim_feedforward"] = int(sd[p + "transformer_ffn_layers.0.linear1.weight"].shape[0])
             break
+    if thing_ids is not None:
+        kw["thing_ids"] = tuple(int(i) for i in thing_ids)
     net = PascoNet(**kw)
     missing, unexpected = net.load_state_dict(remap_reference_state_dict(sd, net), strict=False)
     if missing or unexpected:

@@ -147,6 +147,36 @@ def compute_scene_size(min_c: torch.Tensor, max_c: torch.Tensor, scale: int = 1)
 
 
 # ---- one frame -> one subnet item ---------------------------------------------------------------------------
+def completion_bounds(min_c: torch.Tensor, max_c: torch.Tensor, complete_scale: int = 8):
+    """min_C floored to the completion scale, max_C as it is (kitti_dataset.py:150-175)."""
+    return (torch.floor(min_c.float() / complete_scale) * complete_scale).int(), torch.ceil(max_c)
+
+
+def transformed_labels(semantic_label: np.ndarray, instance_label: np.ndarray, T: torch.Tensor, complete_scale: int = 8):
+    """The label grids resampled under T (kitti_dataset.py:373-395) and the completion bounds taken from them:
+    -> (sem_sparse, sem_coords, ins_sparse, ins_coords, min_C, max_C).  `ins + 1` is uint8 arithmetic, so every sample
+    that lands on an instance id other than 255 survives the `!= 0` filter, id 0 included."""
+    sem = torch.from_numpy(semantic_label)
+    sem_coords = torch.nonzero(sem != 255)
+    sem_sparse, sem_coords, bnd = transform_scene(sem_coords, T, sem.unsqueeze(0) + 1)
+    nz = sem_sparse.sum(dim=1) != 0
+    sem_sparse, sem_coords = sem_sparse[nz] - 1, sem_coords[nz]
+    ins = torch.from_numpy(instance_label)
+    ins_coords = torch.nonzero(ins)
+    if ins_coords.shape[0] > 0:
+        ins_sparse, ins_coords, _ = transform_scene(ins_coords, T, ins.unsqueeze(0) + 1, to_coords_bnd=bnd)
+    else:
+        ins_sparse, ins_coords = torch.zeros((0, 1)), torch.zeros((0, 3)).long()
+    nz = ins_sparse.sum(dim=1) != 0
+    ins_sparse, ins_coords = ins_sparse[nz] - 1, ins_coords[nz]
+    min_c, max_c = sem_coords.min(dim=0)[0], sem_coords.max(dim=0)[0]
+    if ins_coords.shape[0] > 0:
+        min_c = torch.min(min_c, ins_coords.min(dim=0)[0])
+        max_c = torch.max(max_c, ins_coords.max(dim=0)[0])
+    min_c, max_c = completion_bounds(min_c, max_c, complete_scale)
+    return sem_sparse, sem_coords, ins_sparse, ins_coords, min_c, max_c
+
+
 def build_item(xyz: np.ndarray, vote: np.ndarray, intensity: np.ndarray, embedding: np.ndarray,
                semantic_label: np.ndarray, instance_label: np.ndarray, T: Optional[torch.Tensor] = None,
                complete_scale: int = 8, point_labels: Optional[np.ndarray] = None) -> Dict:
@@ -163,19 +193,8 @@ def build_item(xyz: np.ndarray, vote: np.ndarray, intensity: np.ndarray, embeddi
     if point_labels is not None:
         point_labels = point_labels[keep]
 
-    sem = torch.from_numpy(semantic_label)
-    sem_coords = torch.nonzero(sem != 255)
-    sem_sparse, sem_coords, bnd = transform_scene(sem_coords, T, sem.unsqueeze(0) + 1)
-    nz = sem_sparse.sum(dim=1) != 0
-    sem_sparse, sem_coords = sem_sparse[nz] - 1, sem_coords[nz]
-    ins = torch.from_numpy(instance_label)
-    ins_coords = torch.nonzero(ins)
-    if ins_coords.shape[0] > 0:
-        ins_sparse, ins_coords, _ = transform_scene(ins_coords, T, ins.unsqueeze(0) + 1, to_coords_bnd=bnd)
-    else:
-        ins_sparse, ins_coords = torch.zeros((0, 1)), torch.zeros((0, 3)).long()
-    nz = ins_sparse.sum(dim=1) != 0
-    ins_sparse, ins_coords = ins_sparse[nz] - 1, ins_coords[nz]
+    sem_sparse, sem_coords, ins_sparse, ins_coords, min_c, max_c = transformed_labels(semantic_label, instance_label, T,
+                                                                                      complete_scale)
 
     radius = np.linalg.norm(xyz, axis=1)[..., np.newaxis]
     feat = np.concatenate((vote_intensity, radius, embedding), axis=1)
@@ -186,12 +205,6 @@ def build_item(xyz: np.ndarray, vote: np.ndarray, intensity: np.ndarray, embeddi
     in_feat = torch.from_numpy(np.concatenate([feat, return_xyz], axis=1)).float()
     in_coord = transform_coords(torch.from_numpy(coords), T).long()
 
-    min_c, max_c = sem_coords.min(dim=0)[0], sem_coords.max(dim=0)[0]
-    if ins_coords.shape[0] > 0:
-        min_c = torch.min(min_c, ins_coords.min(dim=0)[0])
-        max_c = torch.max(max_c, ins_coords.max(dim=0)[0])
-    min_c = (torch.floor(min_c.float() / complete_scale) * complete_scale).int()
-    max_c = torch.ceil(max_c)
     return {"in_feat": in_feat, "in_coord": in_coord, "T": T, "min_C": min_c, "max_C": max_c,
             "xyz": xyz - origin, "semantic_label_sparse": (sem_sparse.to(torch.uint8), sem_coords),
             "instance_label_sparse": (ins_sparse.to(torch.uint8), ins_coords),
@@ -233,10 +246,37 @@ class FrameReader:
         `semantic_label_origin` / `mask_label_origin` are built from; `pasco_amd.eval.GroundTruth.from_labels` takes them."""
         return read_instance_label_pickle(self.paths(sequence, frame_id)[0])
 
-    def batch(self, sequence: str, frame_id: str, Ts: Sequence[torch.Tensor], embedding_index: int = 0) -> Dict:
+    def batch(self, sequence: str, frame_id: str, Ts: Sequence[torch.Tensor], embedding_index: int = 0,
+              device=None) -> Dict:
+        """`device=None` (or a CPU device) runs the host restatement `build_item`; a GPU device runs the same preparation
+        through the pf_* kernels (`data.device_prep`), bit-equal, with the batch's tensors left on that device."""
         lab, feats, pts = self.paths(sequence, frame_id)
         sem, ins = read_instance_label_pickle(lab)
+        if device is not None and torch.device(device).type == "cuda":
+            plab = read_point_instance_labels(pts) if os.path.exists(pts) else None
+            return prepare_semantic_kitti_on_device(feats, sem, ins, Ts, device, embedding_index, self.complete_scale, plab)
         xyz, vote, intensity, emb = read_waffleiron_features(feats, embedding_index=embedding_index)
         plab = read_point_instance_labels(pts) if os.path.exists(pts) else None
         items = [build_item(xyz, vote, intensity, emb, sem, ins, T, self.complete_scale, plab) for T in Ts]
         return collate(items, self.complete_scale)
+
+
+def prepare_semantic_kitti_on_device(feats_path: str, semantic_label: np.ndarray, instance_label: np.ndarray,
+                                     Ts: Sequence[torch.Tensor], device, embedding_index: int = 0, complete_scale: int = 8,
+                                     point_labels: Optional[np.ndarray] = None) -> Dict:
+    """`collate([build_item(...) for T in Ts])` through the pf_* kernels on `device`.  The WaffleIron arrays go up as they
+    are stored (the embedding as [256, P], read transposed by the kernel) - no host-side concatenation."""
+    from . import device_prep as DP
+    from .frame_lib import _seg, segment
+    with open(feats_path, "rb") as f:
+        data = pickle.load(f)
+    pts = DP.upload(np.ascontiguousarray(data["coords"]), device)
+    vote = DP.upload(np.ascontiguousarray(data["vote"]), device).contiguous()
+    emb = DP.upload(np.ascontiguousarray(data["embedding"][embedding_index]), device).contiguous()    # [256, P]
+    sem, ins = DP.upload(semantic_label, device), DP.upload(instance_label, device)
+    n = int(pts.shape[0])
+    plab = None if point_labels is None else DP.upload(point_labels, device)
+    return DP.prepare(pts, sem, ins, Ts, lo=MIN_EXTENT, hi=MAX_EXTENT, lo_fp64=(0, 0, 0), hi_fp64=(0, 0, 0),
+                      origin=VOX_ORIGIN, voxel=VOXEL_SIZE, centre_fp64=False,
+                      pre=[segment(vote), _seg(pts[:, 3:], 1, 4, 1)], post=[_seg(emb, int(emb.shape[0]), 1, n)],
+                      complete_scale=complete_scale, point_labels=plab)

@@ -1,6 +1,7 @@
 """Score a trained checkpoint on a SemanticKITTI tree and print the reference's three result tables.
 
     python -m pasco_amd.eval.kitti --root <kitti root> --preprocess-root <preprocess root> --ckpt <model.ckpt> [--frames N]
+                                   [--device-prep]
 
 Per frame: `FrameReader.batch` -> `net_from_checkpoint(...).step_inference` -> `SceneEvaluator.add` with the frame's
 `GroundTruth`.  Subnet transforms: subnet 0 sees the frame as it is, subnet i >= 1 under the fixed rotation / translation
@@ -8,6 +9,7 @@ table of the synthetic benchmark (theta_i in (0, 10, -10, 20, -2
 t_i = ((i mod 3 - 1) 0.2, (floor(i / 3) mod 3 - 1) 0.2, 0) m).  This is NOT the reference's validation draw, which samples a
 random transform per subnet and frame, so subnet rows can differ from the paper's by that draw.  The "inference time" column
 is the measured mean wall time of `step_inference` in milliseconds (the reference prints 0.00 there: its caller passes 0).
+`--device-prep` prepares each frame with the pf_* kernels (`FrameReader.batch(device=...)`, bit-equal) instead of on the host.
 """
 from __future__ import annotations
 
@@ -37,7 +39,8 @@ def frames_of(preprocess_root: str, sequence: str):
     return sorted(f[:-len("_1_1.pkl")] for f in os.listdir(d) if f.endswith("_1_1.pkl"))
 
 
-def evaluate(root: str, preprocess_root: str, ckpt: str, sequence: str = "08", frames: int = 0, device: str = "cuda"):
+def evaluate(root: str, preprocess_root: str, ckpt: str, sequence: str = "08", frames: int = 0, device: str = "cuda",
+             device_prep: bool = False):
     """-> (SceneEvaluator, mean step time in ms)."""
     dev = torch.device(device)
     net = net_from_checkpoint(ckpt, device=dev)
@@ -53,7 +56,7 @@ def evaluate(root: str, preprocess_root: str, ckpt: str, sequence: str = "08", f
     for fid in ids:
         sem, ins = reader.labels(sequence, fid)
         net.ensembler.scene_size = tuple(int(v) for v in sem.shape)
-        b = reader.batch(sequence, fid, Ts)
+        b = reader.batch(sequence, fid, Ts, device=dev if device_prep else None)
         with torch.no_grad():
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
@@ -73,8 +76,9 @@ def main(argv=None):
     ap.add_argument("--ckpt", required=True)
     ap.add_argument("--sequence", default="08")
     ap.add_argument("--frames", type=int, default=0, help="first N labelled frames (0 = all)")
+    ap.add_argument("--device-prep", action="store_true", help="prepare frames with the pf_* kernels on the device")
     a = ap.parse_args(argv)
-    ev, step_ms = evaluate(a.root, a.preprocess_root, a.ckpt, a.sequence, a.frames)
+    ev, step_ms = evaluate(a.root, a.preprocess_root, a.ckpt, a.sequence, a.frames, device_prep=a.device_prep)
     print(ev.tables(step_time=step_ms), end="")
 
 
