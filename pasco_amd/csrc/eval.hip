@@ -4,7 +4,9 @@
 // Accumulation: every thread keeps a run of equal keys in registers (neighbouring sites of one thread mostly share the
 // (gt, pred) cell and the confidence bin: empty space) and flushes a run with one LDS integer atomic; a workgroup writes its
 // LDS histogram to its own slab, and k_reduce adds the slabs in block order.  Floating sums are 64-bit fixed point, so
-// there is no float atomic anywhere and every result is bitwise reproducible.  The (gt, pred) intersection table is up to
+// there is no float atomic anywhere and every result is bitwise reproducible.  A slab entry holds at most 2^17 sites
+// (PE_MAX_SITES / MAX_BLOCKS) of |term| <= 2^45, so it fits int64; the sum over slabs does not (2^27 confidences of 1.0
+// are 2^63) and k_reduce adds in 128 bits.  The (gt, pred) intersection table is up to
 // 1024 x 129 cells - larger than LDS - and takes global integer atomics after the same run caching; integer sums do not
 // depend on their order either.
 #include <hip/hip_runtime.h>
@@ -39,19 +41,42 @@ constexpr int MAX_BLOCKS = 1024;
 constexpr int SITES_PER_THREAD = 8;
 constexpr double CONF_SCALE = 68719476736.0;   // 2^36
 constexpr double NLL_SCALE = 1073741824.0;     // 2^30
+constexpr float CONF_LIMIT = 512.0f;           // finite confidences saturate here (pasco_eval.h)
 
 struct Edges {
   float e[NB];
 };
 
 __device__ __forceinline__ int bin_of(float c, const Edges &E) {
+  if (c != c) return NB - 1;  // NaN: torch.bucketize puts it past the last edge
   int n = 0;
 #pragma unroll
   for (int i = 0; i < NB; ++i) n += (E.e[i] <= c) ? 1 : 0;
   return n > 0 ? n - 1 : 0;  // below the first edge (not a probability): bin 0 instead of torch's index -1
 }
 
-__device__ __forceinline__ long long fixed(float v, double scale) { return llrint(static_cast<double>(v) * scale); }
+// Confidence term: NaN and +-inf add nothing, finite values saturate at +-CONF_LIMIT.
+__device__ __forceinline__ long long conf_fixed(float v) {
+  if (!isfinite(v)) return 0;
+  return llrint(static_cast<double>(fminf(fmaxf(v, -CONF_LIMIT), CONF_LIMIT)) * CONF_SCALE);
+}
+
+// -log term: |t| <= 104 for every finite t (-log of the smallest subnormal); NaN and +-inf add nothing.
+__device__ __forceinline__ long long nll_fixed(float t) { return isfinite(t) ? llrint(static_cast<double>(t) * NLL_SCALE) : 0; }
+
+// First maximum of a row, a NaN being the maximum (torch.argmax); -0.0 == +0.0.
+__device__ __forceinline__ int argmax_row(const float *row, int C) {
+  float best = row[0];
+  int pred = 0;
+  for (int c = 1; c < C && best == best; ++c) {
+    const float v = row[c];
+    if (v > best || v != v) {
+      best = v;
+      pred = c;
+    }
+  }
+  return pred;
+}
 
 __device__ __forceinline__ void lds_add(unsigned long long *p, long long v) {
   if (v != 0) atomicAdd(p, static_cast<unsigned long long>(v));
@@ -89,15 +114,7 @@ __global__ __launch_bounds__(BLOCK) void k_ssc(const float *__restrict__ probs, 
     }
     if (g >= C) continue;  // not a class of this output (the host refuses such labels)
     const float *row = probs + s * C;
-    float best = row[0];
-    int pred = 0;
-    for (int c = 1; c < C; ++c) {
-      const float v = row[c];
-      if (v > best) {
-        best = v;
-        pred = c;
-      }
-    }
+    const int pred = argmax_row(row, C);
     const int key = g * C + pred;
     if (key != cm_key) {
       if (cm_key >= 0) lds_add(&cm[cm_key], cm_n);
@@ -119,8 +136,8 @@ __global__ __launch_bounds__(BLOCK) void k_ssc(const float *__restrict__ probs, 
     }
     ++b_n;
     b_cor += (pred == g);
-    b_fx += fixed(cf, CONF_SCALE);
-    const long long l = fixed(-logf(row[g] + 1e-12f), NLL_SCALE);
+    b_fx += conf_fixed(cf);
+    const long long l = nll_fixed(-logf(row[g] + 1e-12f));
     if (grp) nll1 += l; else nll0 += l;
   }
   if (cm_key >= 0) lds_add(&cm[cm_key], cm_n);
@@ -169,7 +186,7 @@ __global__ __launch_bounds__(BLOCK) void k_mask_ece(const int64_t *__restrict__ 
     }
     ++b_n;
     b_cor += (mp == g);
-    b_fx += fixed(cf, CONF_SCALE);
+    b_fx += conf_fixed(cf);
   }
   if (b_key >= 0) {
     lds_add(&s_h[b_key], b_n);
@@ -182,15 +199,16 @@ __global__ __launch_bounds__(BLOCK) void k_mask_ece(const int64_t *__restrict__ 
 }
 
 // Entry i of the slabs summed in block order; entries >= n_int are fixed point: scale_a below n_int + n_a, scale_b above.
+// Counts stay below 2^27; the fixed-point sums are added in 128 bits and rounded to fp64 once.
 __global__ __launch_bounds__(BLOCK) void k_reduce(const long long *__restrict__ slabs, int n_blocks, int slab, int n_int,
                                                   int n_a, double inv_a, double inv_b, int64_t *__restrict__ counts,
                                                   double *__restrict__ sums) {
   const int i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= slab) return;
-  long long acc = 0;
+  __int128 acc = 0;
   for (int b = 0; b < n_blocks; ++b) acc += slabs[(int64_t)b * slab + i];
   if (i < n_int)
-    counts[i] = acc;
+    counts[i] = static_cast<int64_t>(acc);
   else
     sums[i - n_int] = static_cast<double>(acc) * (i - n_int < n_a ? inv_a : inv_b);
 }

@@ -23,6 +23,7 @@ class GroundTruth:
     seg_area: np.ndarray        # [K] int64: voxels of the mask that opened the segment (unknown ones included)
     gt_area: torch.Tensor       # [G + 1] int64 by id (0 for absent ids), on the device of the grids
     shape: tuple
+    max_label: int = -1         # largest semantic label other than 255 (-1: every site unknown)
 
     @property
     def n_gt(self) -> int:
@@ -96,10 +97,12 @@ class GroundTruth:
         ids_a = np.asarray(ids, np.int64)
         gt_area = np.zeros(n_ids + 1, np.int64)
         gt_area[ids_a[present]] = np.asarray(areas, np.int64)[present]
+        labels = np.flatnonzero(cls_count_h[:UNKNOWN])
         return cls(semantic=sem, panoptic=pan, seg_id=ids_a[present], seg_cat=np.asarray(cats, np.int64)[present],
                    seg_thing=np.asarray(isthing, bool)[present], seg_area=np.asarray(areas, np.int64)[present],
-                   gt_area=torch.as_tensor(gt_area, device=dev), shape=shape)
+                   gt_area=torch.as_tensor(gt_area, device=dev), shape=shape,
+                   max_label=int(labels[-1]) if labels.size else -1)
 
     def to(self, device) -> "GroundTruth":
         return GroundTruth(self.semantic.to(device), self.panoptic.to(device), self.seg_id, self.seg_cat, self.seg_thing,
-                           self.seg_area, self.gt_area.to(device), self.shape)
+                           self.seg_area, self.gt_area.to(device), self.shape, self.max_label)

@@ -160,6 +160,7 @@ class SceneEvaluator:
         grid = tuple(int(v) for v in sem_probs[0].shape[1:])
         if grid != tuple(gt.shape):
             raise ValueError(f"output grid {grid} and ground-truth grid {tuple(gt.shape)} differ")
+        self._check_labels(gt)
         S = gt.semantic.numel()
         G = gt.n_gt
         if G > MAX_GT:
@@ -240,12 +241,19 @@ class SceneEvaluator:
         """One scene from its tables (one dict per output, the layout `add` reads back; see tests/eval_restate.py)."""
         if len(tables) != self.n_outputs:
             raise ValueError(f"{len(tables)} outputs, the evaluator holds {self.n_outputs}")
+        self._check_labels(gt)
         gt_cat = dict(zip(gt.seg_id.tolist(), gt.seg_cat.tolist()))
         gt_area = dict(zip(gt.seg_id.tolist(), gt.seg_area.tolist()))
         for acc, t in zip(self.out, tables):
             self._ssc(acc, t)
             self._panoptic(acc, t, gt, gt_cat, gt_area)
         self.scenes += 1
+
+    def _check_labels(self, gt: GroundTruth) -> None:
+        # pe_ssc skips a site labelled c <= label < 255: it would drop out of every table without a word
+        if gt.max_label >= self.n_classes:
+            raise ValueError(f"semantic label {gt.max_label} in the ground truth, the evaluator scores {self.n_classes} "
+                             f"classes (0 .. {self.n_classes - 1}, 255 = unknown)")
 
     def _ssc(self, acc: _Output, t: Dict) -> None:
         cm = np.asarray(t["cm"], np.int64)

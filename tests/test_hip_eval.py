@@ -48,14 +48,15 @@ def fixture_scene(k, dev):
     return outs, probs
 
 
-def assert_tables_equal(got, exp, tol=1e-6):
+def assert_tables_equal(got, exp):
     for key in INT_KEYS:
         assert np.array_equal(np.asarray(got[key]), np.asarray(exp[key])), key
     # the kernels count rows; the restatement counts every known site (pred id 0 included): compare the pred ids >= 1
     assert np.array_equal(got["area"][1:], exp["area"][1:])
     assert np.array_equal(got["inter"][:, 1:], exp["inter"][:, 1:])
-    for key in ("bin_conf", "nll", "mask_conf"):
-        np.testing.assert_allclose(got[key], exp[key], rtol=1e-6, atol=tol * max(1.0, float(np.abs(exp[key]).max())))
+    # sums per bin and group: confidences bit for bit with the fixed-point expectation, -log to the fp32 log's ulp
+    R.check_ssc(got, exp["exact"])
+    R.check_conf_sums(got["mask_conf"], exp["mask_conf_fx"], exp["mask_conf_fp64"], exp["mask_count"], "mask_conf")
     for a, b in zip(got["segments"], exp["segments"]):
         assert a["id"] == b["id"] and a["category_id"] == b["category_id"]
         np.testing.assert_allclose(a["logp"], b["logp"], rtol=1e-6, atol=1e-6)
@@ -120,7 +121,8 @@ def test_row_kernels_odd_sizes_and_bounds(hip, grid, n_pred, n_gt):
     assert np.array_equal(h[o_inter:o_map].reshape(n_gt + 1, n_pred + 1)[:, 1:], exp["inter"][:, 1:])
     assert np.array_equal(h[o_map:o_ec].view(np.int32)[:n_pred + 1], exp["map"])
     assert np.array_equal(h[o_ec:o_ec + 16], exp["mask_count"]) and np.array_equal(h[o_ec + 16:o_es], exp["mask_correct"])
-    np.testing.assert_allclose(h[o_es:o_es + ECE_SUMS].view(np.float64), exp["mask_conf"], rtol=1e-9, atol=1e-9)
+    R.check_conf_sums(h[o_es:o_es + ECE_SUMS].view(np.float64), exp["mask_conf_fx"], exp["mask_conf_fp64"], exp["mask_count"],
+                      "mask_conf")
     # N = 0: empty tables, no launch over rows
     empty = torch.zeros(0, dtype=torch.int64, device=dev)
     lib.panop_pairs(empty, empty.to(torch.int32), sem_d, gid_d, n_pred, n_gt, b + 8 * o_area, b + 8 * o_inter)
@@ -141,6 +143,26 @@ def test_evaluator_refuses_too_many_gt_segments(hip):
     outs, probs = fixture_scene(0, torch.device("cuda"))
     with pytest.raises(ValueError, match="1023"):
         SceneEvaluator(n_outputs=NO).add(outs, [torch.zeros(20, 16, 16, 4, device="cuda")] * NO, gt)
+
+
+def restated_outputs(outs, sem_probs, gt_cpu):
+    """The torch restatement's tables of device outputs moved to the host (dense grids rebuilt from the sparse rows)."""
+    exp_tabs = []
+    for i, o in enumerate(outs):
+        coords, size, min_C, pan, vconf = o.sparse_rows()
+        X, Y, Z = size
+        c = coords[:, 1:].long().cpu() - min_C.cpu().long().reshape(1, 3)
+        inside = (c >= 0).all(1) & (c[:, 0] < X) & (c[:, 1] < Y) & (c[:, 2] < Z)
+        c = c[inside]
+        site = (c[:, 0] * Y + c[:, 1]) * Z + c[:, 2]
+        pan_d = torch.zeros(X * Y * Z, dtype=torch.int32)
+        vconf_d = torch.zeros(X * Y * Z)
+        pan_d[site] = pan.cpu().to(torch.int32)[inside]
+        vconf_d[site] = vconf.cpu().float()[inside]
+        probs = sem_probs[i].permute(1, 2, 3, 0).reshape(-1, sem_probs[i].shape[0]).cpu()
+        exp_tabs.append(R.scene_tables(probs, o["ssc_confidence"].reshape(-1).cpu(), gt_cpu.semantic, pan_d, vconf_d,
+                                       gt_cpu.panoptic, gt_cpu.gt_area.numpy(), o["segments_infos"][0]))
+    return exp_tabs
 
 
 def _s10_step():
@@ -198,21 +220,9 @@ def test_s10_mimo3_step_on_device_equals_the_restatement(hip):
     # the same outputs moved to the host, scored by the restatement
     gt_cpu = gt.to("cpu")
     ref = SceneEvaluator(n_classes=20, thing_ids=net.thing_ids, n_outputs=len(outs))
-    exp_tabs = []
-    for i, o in enumerate(outs):
-        coords, size, min_C, pan, vconf = o.sparse_rows()
-        X, Y, Z = size
-        c = coords[:, 1:].long().cpu()
-        site = (c[:, 0] * Y + c[:, 1]) * Z + c[:, 2]
-        pan_d = torch.zeros(X * Y * Z, dtype=torch.int32)
-        vconf_d = torch.zeros(X * Y * Z)
-        pan_d[site] = pan.cpu().to(torch.int32)
-        vconf_d[site] = vconf.cpu().float()
-        probs = sem_probs[i].permute(1, 2, 3, 0).reshape(-1, 20).cpu()
-        exp_tabs.append(R.scene_tables(probs, o["ssc_confidence"].reshape(-1).cpu(), gt_cpu.semantic, pan_d, vconf_d,
-                                       gt_cpu.panoptic, gt_cpu.gt_area.numpy(), o["segments_infos"][0]))
+    exp_tabs = restated_outputs(outs, sem_probs, gt_cpu)
     for got, exp in zip(first, exp_tabs):
-        assert_tables_equal(got, exp, tol=1e-6)
+        assert_tables_equal(got, exp)
     ref.add_tables(exp_tabs, gt_cpu)
     for a, b in zip(ev.stats(), ref.stats()):
         for key in ("precision", "recall", "iou", "iou_ssc_mean", "empty_ece", "nonempty_ece", "empty_nll", "nonempty_nll"):
