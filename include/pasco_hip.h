@@ -88,8 +88,9 @@ int64_t PH_FN(workspace_bytes)(int64_t n);
  *   uniq_rows[n]  out: input row of unique row j (first n_uniq entries valid)
  *   n_uniq        out: device scalar
  *   status        in/out (or NULL): bit 1 is raised when a coordinate cannot be packed into the 64-bit key (batch index
- *                 outside 0 .. 1023 or a coordinate outside -2^17 .. 2^17 - 1: it would alias another voxel).  Lookups
- *                 (map_find, nbr_build) answer -1 for such coordinates.
+ *                 outside 0 .. 1023, a coordinate outside -2^17 .. 2^17 - 1, or (1023, 2^17 - 1, 2^17 - 1, 2^17 - 1), whose
+ *                 key is the table's empty marker).  Such a row stays out of the table: it is no unique row and its
+ *                 row2uniq is -1.  Lookups (map_find, nbr_build) answer -1 for such coordinates.
  * ------------------------------------------------------------------------------------------- */
 int PH_FN(map_insert)(const int32_t *coords, int64_t n, uint64_t *tkeys, int32_t *tvals,
                       int64_t cap, int32_t *row2uniq, int32_t *uniq_rows, int32_t *n_uniq,

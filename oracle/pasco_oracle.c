@@ -74,10 +74,10 @@ static uint64_t pack(int b, int x, int y, int z) {
          ((uint64_t)((uint32_t)(z + COORD_BIAS) & 0x3FFFFu));
 }
 
-/* batch 0 .. 1023, coordinates -2^17 .. 2^17 - 1: what the key can hold */
+/* batch 0 .. 1023, coordinates -2^17 .. 2^17 - 1: what the key can hold, except the one coordinate whose key is EMPTY_KEY */
 static int packable(int b, int x, int y, int z) {
   return (unsigned)b < 1024u && (unsigned)(x + COORD_BIAS) < (1u << 18) && (unsigned)(y + COORD_BIAS) < (1u << 18) &&
-         (unsigned)(z + COORD_BIAS) < (1u << 18);
+         (unsigned)(z + COORD_BIAS) < (1u << 18) && pack(b, x, y, z) != EMPTY_KEY;
 }
 
 static uint64_t mix(uint64_t k) {
@@ -114,6 +114,10 @@ int pho_map_insert(const int32_t *coords, int64_t n, uint64_t *tkeys, int32_t *t
   int32_t count = 0;
   for (int64_t i = 0; i < n; ++i) {
     const int32_t *c = coords + 4 * i;
+    if (!packable(c[0], c[1], c[2], c[3])) {      /* flagged above, left out of the table */
+      if (row2uniq) row2uniq[i] = -1;
+      continue;
+    }
     uint64_t key = pack(c[0], c[1], c[2], c[3]);
     uint64_t slot = mix(key) & mask;
     while (tkeys[slot] != EMPTY_KEY && tkeys[slot] != key) slot = (slot + 1) & mask;

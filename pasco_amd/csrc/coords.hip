@@ -164,7 +164,11 @@ __global__ void __launch_bounds__(256)
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int4 c = coords[i];
-  if (status != nullptr && !ph_packable(c.x, c.y, c.z, c.w)) atomicOr(status, 2);   // the key would alias another voxel
+  if (!ph_packable(c.x, c.y, c.z, c.w)) {   // its key would alias another voxel or mark a slot unused: left out of the table
+    if (status != nullptr) atomicOr(status, 2);
+    if (row_slot) row_slot[i] = -1;
+    return;
+  }
   uint64_t key = ph_pack(c.x, c.y, c.z, c.w);
   uint64_t slot = ph_hash(key) & mask;
   for (;;) {
@@ -180,7 +184,10 @@ __global__ void __launch_bounds__(256)
 struct PredFirst {
   const int32_t *tvals;
   const int32_t *row_slot;
-  __device__ bool operator()(int, int64_t i) const { return tvals[row_slot[i]] == (int32_t)i; }
+  __device__ bool operator()(int, int64_t i) const {
+    const int32_t s = row_slot[i];
+    return s >= 0 && tvals[s] == (int32_t)i;
+  }
 };
 
 __global__ void __launch_bounds__(256)
@@ -197,7 +204,8 @@ __global__ void __launch_bounds__(256)
                int32_t *__restrict__ row2uniq) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  row2uniq[i] = tvals[row_slot[i]];
+  const int32_t s = row_slot[i];
+  row2uniq[i] = s >= 0 ? tvals[s] : -1;
 }
 
 static inline unsigned nblk(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
@@ -461,6 +469,7 @@ __global__ void __launch_bounds__(256)
     rl_out[i] = vo;
     if ((i & 127) == 0 && (i >> 7) < tcap) tile_k[i >> 7] = k < kvol ? k : -1;
   }
+  for (int64_t t = cap / 128 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < tcap; t += stride) tile_k[t] = -1;   // past the list
 }
 
 extern "C" int ph_rowlist_pack(const int32_t *pairs_in, const int32_t *pairs_out, const int32_t *counts, int32_t kvol,

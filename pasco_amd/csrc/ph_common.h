@@ -56,10 +56,11 @@ __host__ __device__ __forceinline__ uint64_t ph_pack(int b, int x, int y, int z)
          ((uint64_t)((uint32_t)(z + PH_COORD_BIAS) & 0x3FFFFu));
 }
 
-// what ph_pack can represent: batch 0 .. 1023, coordinates -2^17 .. 2^17 - 1 (anything else would alias another key)
+// what ph_pack can represent: batch 0 .. 1023, coordinates -2^17 .. 2^17 - 1 (anything else would alias another key), except
+// (1023, 2^17 - 1, 2^17 - 1, 2^17 - 1), whose key is all ones: PH_EMPTY_KEY, the table's marker of an unused slot
 __host__ __device__ __forceinline__ bool ph_packable(int b, int x, int y, int z) {
   return (unsigned)b < 1024u && (unsigned)(x + PH_COORD_BIAS) < (1u << 18) && (unsigned)(y + PH_COORD_BIAS) < (1u << 18) &&
-         (unsigned)(z + PH_COORD_BIAS) < (1u << 18);
+         (unsigned)(z + PH_COORD_BIAS) < (1u << 18) && ph_pack(b, x, y, z) != PH_EMPTY_KEY;
 }
 
 __host__ __device__ __forceinline__ uint64_t ph_hash(uint64_t k) {

@@ -40,21 +40,30 @@ def unique_rows_sorted(rows: torch.Tensor):
     """`torch.unique(rows, return_inverse=True, dim=0)` for integer coordinate rows [N, 3] (x,y,z) or [N, 4]
     (b,x,y,z): same sorted unique rows and inverse, via ONE 64-bit key per row (the coordinate-map packing:
     10 bits batch, 18 bits per axis biased by 2^17 - order preserving) and a 1-D sort instead of a row-wise
-    lexicographic sort."""
+    lexicographic sort.  Raises ValueError for a row the key cannot hold (batch outside 0 .. 1023, a coordinate outside
+    -2^17 .. 2^17 - 1)."""
     r = rows.to(torch.int64)
     if r.shape[1] == 3:
         b, xyz = None, r
     else:
         b, xyz = r[:, 0], r[:, 1:]
     bias = 1 << 17
-    key = ((xyz[:, 0] + bias) << 36) | ((xyz[:, 1] + bias) << 18) | (xyz[:, 2] + bias)
+    u = xyz + bias
+    bad = ((u >> 18) != 0).any()
+    key = (u[:, 0] << 36) | (u[:, 1] << 18) | u[:, 2]
     if b is not None:
+        bad = bad | ((b >> 10) != 0).any()
         key = key | (b << 54)
-    uk, inv = torch.unique(key, return_inverse=True)
+    # batches >= 512 set bit 63: flipped, the signed order of the int64 keys is the unsigned order of the packed rows
+    sign = -(1 << 63)
+    uk, inv = torch.unique(key ^ sign, return_inverse=True)
+    if bool(bad):
+        raise ValueError("unique_rows_sorted: a row outside batch 0..1023 / coordinates -131072..131071")
+    uk = uk ^ sign
     mask = (1 << 18) - 1
     cols = [((uk >> 36) & mask) - bias, ((uk >> 18) & mask) - bias, (uk & mask) - bias]
     if b is not None:
-        cols = [uk >> 54] + cols
+        cols = [(uk >> 54) & 0x3FF] + cols
     return torch.stack(cols, dim=1).to(rows.dtype), inv
 
 

@@ -654,8 +654,8 @@ class CBackend:
     STATUS_TEXT = {
         1: "an activation outside the f16 range in a split-precision convolution / attention operand (rerun with "
            "pasco_amd.graph.fused.set_conv_precision('f32'); PascoNet.forward does so by itself)",
-        2: "a coordinate outside the packable range (batch index 0..1023, coordinates -131072..131071) was inserted into a "
-           "coordinate map; it would alias another voxel",
+        2: "a coordinate outside the packable range (batch index 0..1023, coordinates -131072..131071, not all four at their "
+           "maximum) was inserted into a coordinate map; the row was left out of the map",
         32: "a kernel map handed over as one-pair-per-output-row (fused.conv(..., one_pair=True): row lists of a generative "
             "transposed convolution) has another number of pairs than rows: output rows would stay unwritten (PASCO_CONV_RL=0)",
         16: "an optimistic shortcut of the graph did not hold (a fast path taken without the host read that would justify it: "
