@@ -5,9 +5,11 @@ from .semantic_kitti import (build_item, collate, pack_bits, read_instance_label
                              read_occluded, read_occupancy, read_point_instance_labels, read_pointcloud,
                              read_waffleiron_features, transform_coords, transform_scene, unpack_bits, FrameReader)
 from .kitti360 import Kitti360FrameReader, build_item_kitti360, read_match_file, read_velodyne
+from .instances import instance_labels, remap_lut, semantic_grid, write_instance_pickle
 from .checkpoint import load_lightning_state_dict, net_from_checkpoint, remap_reference_state_dict
 
 __all__ = ["build_item", "collate", "pack_bits", "unpack_bits", "read_instance_label_pickle", "read_invalid",
            "read_label", "read_occluded", "read_occupancy", "read_point_instance_labels", "read_pointcloud",
            "read_waffleiron_features", "transform_coords", "transform_scene", "FrameReader",
-           "Kitti360FrameReader", "build_item_kitti360", "read_match_file", "read_velodyne", "load_lightning_state_dict", "net_from_checkpoint", "remap_reference_state_dict"]
+           "Kitti360FrameReader", "build_item_kitti360", "read_match_file", "read_velodyne", "instance_labels", "remap_lut",
+           "semantic_grid", "write_instance_pickle", "load_lightning_state_dict", "net_from_checkpoint", "remap_reference_state_dict"]

@@ -100,9 +100,15 @@ class Kitti360FrameReader:
     and the match file `sequence raw_id sscbench_id`, whose path the caller passes.  `batch(seq, frame, Ts)` returns the
     collated a0 contract for len(Ts) subnets, each fed the same frame under its own transform."""
 
-    def __init__(self, root: str, preprocess_root: str, label_root: str, match_file: str, complete_scale: int = 8):
+    def __init__(self, root: str, preprocess_root: str, label_root: str, match_file: str, complete_scale: int = 8,
+                 instances: str = "file", label_device="cuda"):
+        """`instances="file"` reads the label grids from the instance pickle; `"device"` builds them from
+        `<label_root>/labels/<seq>/<frame>_1_1.npy` with the pl_* kernels on `label_device` (`data.instances`)."""
+        if instances not in ("file", "device"):
+            raise ValueError(f"instances={instances!r}: 'file' or 'device'")
         self.root, self.preprocess_root, self.label_root = root, preprocess_root, label_root
         self.complete_scale = complete_scale
+        self.instances, self.label_device, self._last = instances, label_device, (None, None)
         self.match = read_match_file(match_file)
 
     def frames(self, split: str) -> List[tuple]:
@@ -122,11 +128,18 @@ class Kitti360FrameReader:
 
     def labels(self, sequence: str, frame_id: str):
         """The frame's origin label grids (semantic uint8, 255 = unknown; instance ids) for `GroundTruth.from_labels`."""
+        if self.instances == "device":
+            from . import instances as I
+            if self._last[0] != (sequence, frame_id):       # labels() and batch() of one frame share one run
+                grid = np.load(os.path.join(self.label_root, "labels", sequence, f"{frame_id}_1_1.npy")).astype(np.uint8)
+                ins, sem, _ = I.instance_labels(grid, THING_IDS, I.MIN_SIZE, self.label_device)
+                self._last = ((sequence, frame_id), I.as_label_pair(ins, sem))
+            return self._last[1]
         return read_instance_label_pickle(self.paths(sequence, frame_id)[0])
 
     def batch(self, sequence: str, frame_id: str, Ts: Sequence[torch.Tensor], device=None) -> Dict:
-        lab, pcp = self.paths(sequence, frame_id)
-        sem, ins = read_instance_label_pickle(lab)
+        _, pcp = self.paths(sequence, frame_id)
+        sem, ins = self.labels(sequence, frame_id)
         pc = read_velodyne(pcp)
         if device is not None and torch.device(device).type == "cuda":
             return prepare_kitti360_on_device(pc, sem, ins, Ts, device, self.complete_scale)

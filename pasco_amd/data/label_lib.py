@@ -1,0 +1,105 @@
+"""ctypes binding of include/pasco_label.h (the `pl_*` entry points of libpascohip.so): label generation on the device.
+
+Kept apart from `me.backend` like `data.frame_lib`: the CPU oracle binds `me.backend._SIGNATURES` and has no label kernels.
+Every method takes device tensors and enqueues on the caller's current stream; nothing synchronises."""
+from __future__ import annotations
+
+import ctypes as C
+import threading
+from typing import Optional, Sequence
+
+import torch
+
+from ..me.backend import HIP_LIB_PATH
+
+PL_ABI_VERSION = 1       # include/pasco_label.h PL_ABI_VERSION this binding was written against
+MAX_THINGS = 32
+RECORD = 4
+REC_INSTANCES, REC_DROPPED, REC_UNKNOWN, REC_STATUS = 0, 1, 2, 3
+STATUS_RAW_RANGE, STATUS_LOOP_CAP = 1, 2
+
+_vp, _i64, _i32 = C.c_void_p, C.c_int64, C.c_int32
+_SIGNATURES = {
+    "abi_version": ([], C.c_int),
+    "last_error": ([], C.c_char_p),
+    "semantic_grid": ([_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp], C.c_int),
+    "instances_workspace_bytes": ([_i32, _i32, _i32, _i32], _i64),
+    "instances": ([_vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp], C.c_int),
+}
+
+
+class LabelLib:
+    def __init__(self, path: str = HIP_LIB_PATH):
+        self.lib = C.CDLL(path)
+        for name, (args, res) in _SIGNATURES.items():
+            fn = getattr(self.lib, "pl_" + name)
+            fn.argtypes, fn.restype = args, res
+        v = self.lib.pl_abi_version()
+        if v != PL_ABI_VERSION:
+            raise RuntimeError(f"{path}: pl ABI {v}, this binding needs {PL_ABI_VERSION}; rebuild (pasco_amd/build.py)")
+
+    def _ok(self, rc: int, what: str):
+        if rc != 0:
+            raise RuntimeError(f"pl_{what}: {self.lib.pl_last_error().decode()}")
+
+    @staticmethod
+    def _stream(t: torch.Tensor):
+        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+    def semantic_grid(self, raw: torch.Tensor, invalid: torch.Tensor, lut: torch.Tensor,
+                      status: Optional[torch.Tensor] = None):
+        """raw uint16 [S] (or int16 holding the same bits), invalid uint8 [S / 8], lut uint8 [n] on the device ->
+        (sem uint8 [S], status int32 [1]); a non-zero status means a raw label outside the table (see pasco_label.h)."""
+        assert raw.is_cuda and raw.dtype in (torch.uint16, torch.int16) and raw.is_contiguous() and raw.dim() == 1
+        assert invalid.is_cuda and invalid.dtype == torch.uint8 and invalid.is_contiguous()
+        assert lut.is_cuda and lut.dtype == torch.uint8 and lut.is_contiguous()
+        S = int(raw.numel())
+        if invalid.numel() * 8 != S:
+            raise ValueError(f"pl_semantic_grid: {S} labels but {invalid.numel()} bytes of invalid bits")
+        sem = torch.empty(S, dtype=torch.uint8, device=raw.device)
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=raw.device)
+        self._ok(self.lib.pl_semantic_grid(raw.data_ptr(), invalid.data_ptr(), lut.data_ptr(), int(lut.numel()), S,
+                                           sem.data_ptr(), status.data_ptr(), self._stream(raw)), "semantic_grid")
+        return sem, status
+
+    def workspace_bytes(self, shape: Sequence[int], n_things: int) -> int:
+        X, Y, Z = (int(v) for v in shape)
+        n = int(self.lib.pl_instances_workspace_bytes(X, Y, Z, int(n_things)))
+        if n < 0:
+            raise ValueError(f"pl_instances: grid {X} x {Y} x {Z} with {n_things} thing ids is not supported")
+        return n
+
+    def instances(self, sem: torch.Tensor, thing_ids: Sequence[int], min_size: int = 8, sizes_cap: int = 0,
+                  ws: Optional[torch.Tensor] = None):
+        """sem uint8 [X, Y, Z] on the device -> (instance int32 [X, Y, Z], semantic uint8 [X, Y, Z], record int32 [4],
+        sizes int32 [sizes_cap] or None), all on the device."""
+        assert sem.is_cuda and sem.dtype == torch.uint8 and sem.is_contiguous() and sem.dim() == 3
+        ids = [int(t) for t in thing_ids]
+        need = self.workspace_bytes(sem.shape, len(ids))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=sem.device)
+        assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous()
+        ins = torch.empty(sem.shape, dtype=torch.int32, device=sem.device)
+        out = torch.empty_like(sem)
+        rec = torch.empty(RECORD, dtype=torch.int32, device=sem.device)
+        sizes = torch.zeros(sizes_cap, dtype=torch.int32, device=sem.device) if sizes_cap > 0 else None
+        X, Y, Z = (int(v) for v in sem.shape)
+        self._ok(self.lib.pl_instances(sem.data_ptr(), X, Y, Z, (_i32 * max(len(ids), 1))(*ids), len(ids), int(min_size),
+                                       ins.data_ptr(), out.data_ptr(), rec.data_ptr(),
+                                       None if sizes is None else sizes.data_ptr(), int(sizes_cap), ws.data_ptr(),
+                                       ws.numel(), self._stream(sem)), "instances")
+        return ins, out, rec, sizes
+
+
+_LIB = None
+_LOCK = threading.Lock()
+
+
+def label_lib() -> LabelLib:
+    """The process-wide binding of libpascohip.so's label kernels (a missing library is an error)."""
+    global _LIB
+    with _LOCK:
+        if _LIB is None:
+            _LIB = LabelLib()
+        return _LIB

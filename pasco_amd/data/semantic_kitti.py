@@ -233,25 +233,49 @@ class FrameReader:
     `batch(seq, frame, Ts)` returns the collated a0 contract for len(Ts) subnets (the reference's validation loader
     feeds every subnet the same frame under its own transform)."""
 
-    def __init__(self, root: str, preprocess_root: str, complete_scale: int = 8):
+    def __init__(self, root: str, preprocess_root: str, complete_scale: int = 8, instances: str = "file",
+                 config: Optional[str] = None, grid=(256, 256, 32), thing_ids=(1, 2, 3, 4, 5, 6, 7, 8), label_device="cuda"):
+        """`instances="file"` reads the label grids from the instance pickle; `"device"` builds them from the dataset's own
+        `voxels/<frame>.label` / `.invalid` with the pl_* kernels on `label_device` (`data.instances`; `config` is the
+        dataset's semantic-kitti.yaml), so no instance_labels_v2 directory is needed."""
+        if instances not in ("file", "device"):
+            raise ValueError(f"instances={instances!r}: 'file' or 'device'")
+        if instances == "device" and config is None:
+            raise ValueError("instances='device' needs the dataset's semantic-kitti.yaml (config=...)")
         self.root, self.preprocess_root, self.complete_scale = root, preprocess_root, complete_scale
+        self.instances, self.grid, self.thing_ids, self.label_device = instances, tuple(grid), tuple(thing_ids), label_device
+        self._lut, self._config, self._last = None, config, (None, None)
 
     def paths(self, sequence: str, frame_id: str):
         return (os.path.join(self.preprocess_root, "instance_labels_v2", sequence, f"{frame_id}_1_1.pkl"),
                 os.path.join(self.preprocess_root, "waffleiron_v2/sequences", sequence, "seg_feats_tta", f"{frame_id}.pkl"),
                 os.path.join(self.root, "dataset", "sequences", sequence, "labels", f"{frame_id}.label"))
 
+    def _device_labels(self, sequence: str, frame_id: str):
+        from . import instances as I
+        if self._last[0] != (sequence, frame_id):       # labels() and batch() of one frame share one run
+            if self._lut is None:
+                self._lut = I.remap_lut(self._config)
+            vox = os.path.join(self.root, "dataset", "sequences", sequence, "voxels")
+            sem = I.semantic_grid(os.path.join(vox, frame_id + ".label"), os.path.join(vox, frame_id + ".invalid"),
+                                  self._lut, self.label_device, self.grid)
+            ins, sem, _ = I.instance_labels(sem, self.thing_ids, I.MIN_SIZE, self.label_device)
+            self._last = ((sequence, frame_id), I.as_label_pair(ins, sem))
+        return self._last[1]
+
     def labels(self, sequence: str, frame_id: str):
         """The frame's origin label grids (semantic uint8 with 255 = unknown, instance ids): what the reference's
         `semantic_label_origin` / `mask_label_origin` are built from; `pasco_amd.eval.GroundTruth.from_labels` takes them."""
+        if self.instances == "device":
+            return self._device_labels(sequence, frame_id)
         return read_instance_label_pickle(self.paths(sequence, frame_id)[0])
 
     def batch(self, sequence: str, frame_id: str, Ts: Sequence[torch.Tensor], embedding_index: int = 0,
               device=None) -> Dict:
         """`device=None` (or a CPU device) runs the host restatement `build_item`; a GPU device runs the same preparation
         through the pf_* kernels (`data.device_prep`), bit-equal, with the batch's tensors left on that device."""
-        lab, feats, pts = self.paths(sequence, frame_id)
-        sem, ins = read_instance_label_pickle(lab)
+        _, feats, pts = self.paths(sequence, frame_id)
+        sem, ins = self.labels(sequence, frame_id)
         if device is not None and torch.device(device).type == "cuda":
             plab = read_point_instance_labels(pts) if os.path.exists(pts) else None
             return prepare_semantic_kitti_on_device(feats, sem, ins, Ts, device, embedding_index, self.complete_scale, plab)

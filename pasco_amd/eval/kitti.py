@@ -1,7 +1,7 @@
 """Score a trained checkpoint on a SemanticKITTI tree and print the reference's three result tables.
 
     python -m pasco_amd.eval.kitti --root <kitti root> --preprocess-root <preprocess root> --ckpt <model.ckpt> [--frames N]
-                                   [--device-prep]
+                                   [--device-prep] [--instances-on-device --config <semantic-kitti.yaml>]
 
 Per frame: `FrameReader.batch` -> `net_from_checkpoint(...).step_inference` -> `SceneEvaluator.add` with the frame's
 `GroundTruth`.  Subnet transforms: subnet 0 sees the frame as it is, subnet i >= 1 under the fixed rotation / translation
@@ -10,6 +10,9 @@ t_i = ((i mod 3 - 1) 0.2, (floor(i / 3) mod 3 - 1) 0.2, 0) m).  This is NOT the 
 random transform per subnet and frame, so subnet rows can differ from the paper's by that draw.  The "inference time" column
 is the measured mean wall time of `step_inference` in milliseconds (the reference prints 0.00 there: its caller passes 0).
 `--device-prep` prepares each frame with the pf_* kernels (`FrameReader.batch(device=...)`, bit-equal) instead of on the host.
+`--instances-on-device` builds the panoptic ground truth from the dataset's own `voxels/<frame>.label` / `.invalid` with the
+pl_* kernels (`data.instances`) instead of reading `instance_labels_v2/*.pkl`; frames are then listed from the dataset tree
+(`float(frame) % 5 == 0`, as the reference's generator selects them).
 """
 from __future__ import annotations
 
@@ -34,18 +37,27 @@ def subnet_transforms(m: int):
     return Ts
 
 
-def frames_of(preprocess_root: str, sequence: str):
+def frames_of(preprocess_root: str, sequence: str, root: str = None, frame_interval: int = 5):
+    """Labelled frames of a sequence: from the instance pickles, or (with `root`) from the dataset tree itself."""
+    if root is not None:
+        from ..data.gen_instances import kitti_frames
+        return kitti_frames(root, sequence, frame_interval)
     d = os.path.join(preprocess_root, "instance_labels_v2", sequence)
     return sorted(f[:-len("_1_1.pkl")] for f in os.listdir(d) if f.endswith("_1_1.pkl"))
 
 
 def evaluate(root: str, preprocess_root: str, ckpt: str, sequence: str = "08", frames: int = 0, device: str = "cuda",
-             device_prep: bool = False):
+             device_prep: bool = False, instances: str = "file", config: str = None, grid=(256, 256, 32)):
     """-> (SceneEvaluator, mean step time in ms)."""
     dev = torch.device(device)
     net = net_from_checkpoint(ckpt, device=dev)
-    reader = FrameReader(root, preprocess_root)
-    ids = frames_of(preprocess_root, sequence)
+    if instances == "device":
+        reader = FrameReader(root, preprocess_root, instances="device", config=config, grid=grid,
+                             thing_ids=net.thing_ids, label_device=dev)
+        ids = frames_of(preprocess_root, sequence, root=root)
+    else:
+        reader = FrameReader(root, preprocess_root)
+        ids = frames_of(preprocess_root, sequence)
     if frames:
         ids = ids[:frames]
     if not ids:
@@ -77,8 +89,16 @@ def main(argv=None):
     ap.add_argument("--sequence", default="08")
     ap.add_argument("--frames", type=int, default=0, help="first N labelled frames (0 = all)")
     ap.add_argument("--device-prep", action="store_true", help="prepare frames with the pf_* kernels on the device")
+    ap.add_argument("--instances-on-device", action="store_true",
+                    help="build the instance labels from the dataset's voxel files with the pl_* kernels (needs --config)")
+    ap.add_argument("--config", help="the dataset's semantic-kitti.yaml (learning_map), for --instances-on-device")
+    ap.add_argument("--grid", default="256,256,32", help="X,Y,Z of a voxel file, for --instances-on-device")
     a = ap.parse_args(argv)
-    ev, step_ms = evaluate(a.root, a.preprocess_root, a.ckpt, a.sequence, a.frames, device_prep=a.device_prep)
+    if a.instances_on_device and not a.config:
+        ap.error("--instances-on-device needs --config")
+    ev, step_ms = evaluate(a.root, a.preprocess_root, a.ckpt, a.sequence, a.frames, device_prep=a.device_prep,
+                           instances="device" if a.instances_on_device else "file", config=a.config,
+                           grid=tuple(int(v) for v in a.grid.split(",")))
     print(ev.tables(step_time=step_ms), end="")
 
 

@@ -2,7 +2,7 @@
 
     python -m pasco_amd.eval.kitti360 --root <KITTI-360 root> --preprocess-root <preprocess root> --label-root <SSCBench root>
                                       --match-file <kitti_360_match.txt> --ckpt <model.ckpt> [--split val|test] [--frames N]
-                                      [--host-prep]
+                                      [--host-prep] [--instances-on-device]
 
 Per frame: `Kitti360FrameReader.batch` -> `net_from_checkpoint(..., thing_ids=(1..6)).step_inference` -> `SceneEvaluator.add`
 with the frame's `GroundTruth`, under the 19 KITTI-360 class names.  Frames are prepared on the device by default (the pf_*
@@ -10,6 +10,8 @@ kernels, bit-equal to the host restatement; `--host-prep` runs that restatement 
 of `eval.kitti` (subnet 0 sees the frame as it is).  This is NOT the reference's validation draw, which samples a random
 rotation of up to 10 degrees, a translation and flips per subnet and frame, so subnet rows can differ from the paper's by that
 draw.  The "inference time" column is the measured mean wall time of `step_inference` in milliseconds.
+`--instances-on-device` builds the panoptic ground truth from `<label-root>/labels/<seq>/<frame>_1_1.npy` with the pl_* kernels
+(`data.instances`) instead of reading `instance_labels_v2/*.pkl`.
 """
 from __future__ import annotations
 
@@ -27,13 +29,13 @@ from .metrics import SceneEvaluator
 
 
 def evaluate(root: str, preprocess_root: str, label_root: str, match_file: str, ckpt: str, split: str = "test",
-             frames: int = 0, device: str = "cuda", device_prep: bool = True):
+             frames: int = 0, device: str = "cuda", device_prep: bool = True, instances: str = "file"):
     """-> (SceneEvaluator, mean step time in ms)."""
     dev = torch.device(device)
     net = net_from_checkpoint(ckpt, device=dev, thing_ids=THING_IDS)
     if net.n_classes != len(CLASS_NAMES):
         raise ValueError(f"{ckpt}: {net.n_classes} classes, a KITTI-360 checkpoint has {len(CLASS_NAMES)}")
-    reader = Kitti360FrameReader(root, preprocess_root, label_root, match_file)
+    reader = Kitti360FrameReader(root, preprocess_root, label_root, match_file, instances=instances, label_device=dev)
     ids = reader.frames(split)
     if frames:
         ids = ids[:frames]
@@ -69,9 +71,11 @@ def main(argv=None):
     ap.add_argument("--split", default="test", choices=("val", "test"))
     ap.add_argument("--frames", type=int, default=0, help="first N labelled frames (0 = all)")
     ap.add_argument("--host-prep", action="store_true", help="prepare frames on the host instead of with the pf_* kernels")
+    ap.add_argument("--instances-on-device", action="store_true",
+                    help="build the instance labels from the label .npy files with the pl_* kernels")
     a = ap.parse_args(argv)
     ev, step_ms = evaluate(a.root, a.preprocess_root, a.label_root, a.match_file, a.ckpt, a.split, a.frames,
-                           device_prep=not a.host_prep)
+                           device_prep=not a.host_prep, instances="device" if a.instances_on_device else "file")
     print(ev.tables(step_time=step_ms), end="")
 
 
