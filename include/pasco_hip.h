@@ -387,9 +387,15 @@ int PH_FN(dense_gather)(const float *dense, int32_t c, const int32_t *h_dims4,
  *   q [B, H, Qn, Dh] (pre-scaled by 1/sqrt(Dh)), k / v [B, N, H*Dh], out [B, Qn, H*Dh]
  *   bits [B, N, 4]: bit q of the 128-bit word = query q may attend that key (NULL = no mask)
  *   any  [B, 4]   : OR of bits over the keys; a query with no allowed key attends everywhere
- *                   (transformer_predictor_v2.py:163-164)
+ *                   (transformer_predictor_v2.py:163-164).  With bits given and any = NULL that rule is off: a query
+ *                   with no allowed key gets an output row of exact zeros (all three attention entry points).
+ *   Bits at positions >= Qn of a word, in bits or in any, are never looked at.  q, k and v must be finite.
+ *   ws / ws_bytes : scratch of at least attn_workspace_bytes; a smaller one is refused (non-zero return, nothing launched).
  * attn_mask_pack builds bits / any from vals [B*N, Qn]: allowed = (vals != 0), or (vals > 0) when
- * `positive_only` (mask logits: sigmoid(l) > 0.5 <=> l > 0, transformer_predictor_v2.py:226).
+ * `positive_only` (mask logits: sigmoid(l) > 0.5 <=> l > 0, transformer_predictor_v2.py:226).  The comparisons are the
+ * IEEE ones on the fp32 value as stored: -0.0 is zero, a denormal is not (and is positive when its sign is), +-inf are
+ * non-zero, and NaN is non-zero but not positive - a NaN logit allows under the first rule and forbids under
+ * `positive_only`.  Bits at positions >= Qn are written as 0.
  * bits_orpool ORs the bit rows of the children of every coarse voxel (the reference max-pools the
  * 0/1 mask, transformer_predictor_v2.py:232-236); bits_or_reduce ORs all rows of a batch (`any`).
  * ------------------------------------------------------------------------------------------- */

@@ -779,8 +779,10 @@ int pho_attn_mask_pack(const float *vals, int64_t n, int32_t b, int32_t qn, int3
 int pho_attn_cross_fwd(const float *q, const float *k, const float *v, const uint32_t *bits, const uint32_t *any,
                        float *out, int64_t n, int32_t b, int32_t h, int32_t qn, int32_t dh, void *ws,
                        int64_t ws_bytes, ph_stream_t stream) {
-  (void)ws; (void)ws_bytes; (void)stream;
+  (void)ws; (void)stream;
   if (qn < 1 || qn > 128 || dh < 1 || dh > 512) return fail("attn_cross_fwd: bad shape");
+  /* no scratch is used here, but a buffer below the declared size is refused as the library refuses it (pasco_hip.h) */
+  if (ws_bytes < pho_attn_workspace_bytes(n, b, h, qn, dh)) return fail("attn_cross_fwd: workspace too small");
   const int D = h * dh;
 #pragma omp parallel for collapse(2) schedule(dynamic)
   for (int bi = 0; bi < b; ++bi)
@@ -849,9 +851,10 @@ static float f16_to_f32_at(const void *p, int64_t i) { return f16_bits_to_f32(((
 int pho_attn_cross_feat(const float *q2, const void *x_split, const void *aug, int32_t c, int32_t exp2, const uint32_t *bits,
                         const uint32_t *any, float *out, int64_t n, int32_t b, int32_t h, int32_t qn, void *ws,
                         int64_t ws_bytes, int32_t *status, ph_stream_t stream) {
-  (void)ws; (void)ws_bytes; (void)status; (void)stream;
+  (void)ws; (void)status; (void)stream;
   if (c < 32 || c % 32 != 0 || c > 1024) return fail("attn_cross_feat: channels must be a multiple of 32 (<= 1024)");
   if (qn < 1 || qn > 128 || b < 1 || h < 1 || n < 1) return fail("attn_cross_feat: bad shape");
+  if (ws_bytes < pho_attn_workspace_bytes(n, b, h, qn, c + 16)) return fail("attn_cross_feat: workspace too small");
   const int d = c + 16;
   float *x = unsplit_rows(x_split, (int64_t)b * n, c, ldexpf(1.f, -exp2));
   const float aug_unscale = ldexpf(1.f, -exp2);         /* the position columns carry the operand's scale (pho_pos_aug) */

@@ -3,6 +3,8 @@ fp32 reference of the same op and against the CPU oracle."""
 import pytest
 import torch
 
+from tests.attn_ref64 import feat_ref, unsplit as _unsplit
+
 pytestmark = pytest.mark.gpu
 
 
@@ -89,12 +91,6 @@ def test_attn_workspace_is_large_enough(hip, Q):
     ref = torch.nn.functional.scaled_dot_product_attention(
         q, k.view(B, N, H, Dh).transpose(1, 2), v.view(B, N, H, Dh).transpose(1, 2), scale=1.0)
     assert torch.allclose(out, ref.transpose(1, 2).reshape(B, Q, H * Dh), rtol=1e-4, atol=1e-4)
-
-
-def _unsplit(op, c, exp2):
-    """split operand [rows, c/32, 2, 32] f16 -> the fp32 values it stands for."""
-    x = op.float()
-    return ((x[:, :, 0] + x[:, :, 1]).reshape(op.shape[0], c) * float(2.0 ** -exp2))
 
 
 @pytest.mark.parametrize("B,H,Q,N", [(1, 8, 100, 1), (2, 8, 100, 31), (2, 8, 100, 32), (3, 8, 100, 33),
@@ -195,23 +191,6 @@ def test_bits_block_or_matches_oracle_and_pooling(hip, oracle, s):
 
 
 # ---- attention on the level's feature operand (ph_attn_cross_feat, ph_pos_aug) ---------------------------------------
-def feat_ref(q2, x_split, aug, B, N, allow):
-    """fp64 restatement: rows r = [x | aug] (x = hi + lo of the operand, unscaled), Y = softmax(q2 r^T + mask) r."""
-    from pasco_amd.me.backend import SPLIT_ACT_EXP2
-    xs = x_split.double()
-    x = (xs[:, :, 0] + xs[:, :, 1]).reshape(B, N, -1) * 2.0 ** -SPLIT_ACT_EXP2
-    # the position columns carry the operand's 2^exp2 like the feature columns (ph_pos_aug, round 5)
-    r = torch.cat([x, aug.double().reshape(B, N, 16) * 2.0 ** -SPLIT_ACT_EXP2], dim=-1)             # [B, N, E]
-    s = torch.einsum("bhqe,bne->bhqn", q2.double(), r)
-    if allow is not None:
-        al = allow.permute(0, 2, 1)
-        al = al | ~al.any(dim=-1, keepdim=True)
-        s = s.masked_fill(~al[:, None], float("-inf"))
-    y = torch.einsum("bhqn,bne->bhqe", torch.softmax(s, dim=-1), r)        # [B, H, Q, E]
-    H, Q, E = y.shape[1:]
-    return y.permute(0, 2, 1, 3).reshape(B, Q, H * E).float()
-
-
 def feat_inputs(B, H, Q, N, seed, hip):
     from pasco_amd.graph.transformer import PositionEmbeddingSineSparse
     g = torch.Generator().manual_seed(seed)
