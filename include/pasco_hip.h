@@ -355,6 +355,10 @@ typedef struct ph_sem_ens_desc {
   float *conf[9]; /* each may be NULL */
 } ph_sem_ens_desc;
 
+/* Every row maximum is a maximum of the values WRITTEN (conf[i][s] is bit-equal to the largest entry of out[i][s, :]); a site
+ * where every subnet is absent gets the exact one-hot of class 0 in all m + 1 outputs and confidence 1.  logits[i] and out[i]
+ * need 4-byte alignment only: rows that are not 16-byte aligned take a scalar path that writes the same bits.  The library
+ * serves c = 19 and 20. */
 int PH_FN(sem_ensemble)(const ph_sem_ens_desc *desc, ph_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -462,7 +466,10 @@ int PH_FN(pos_aug)(const int32_t *coords, int64_t n, const float *eps, int32_t t
  * which works on dense [100, 256, 256, 32] tensors per subnet).  sel [U] = canonical site id of every union row.
  *   ens_resample: out[u, :] = sigmoid(logits[rows[sel[u]], :]) (rows [n_sites]: the subnet's voxel row of a canonical
  *                 site or -1 -> zeros) = sigmoid + grid_sample(nearest, zero padding) of ensembler.py:44-62;
- *                 flag[u] = the row has a non-zero entry (what ME.to_sparse keeps, misc.py:46-57)
+ *                 flag[u] = the row has a non-zero entry (what ME.to_sparse keeps, misc.py:46-57).  The value is the fp32
+ *                 quotient 1 / (1 + expf(-x)): once expf(-x) overflows (x below about -88.73) it is an exact 0 - where
+ *                 torch.sigmoid still returns a denormal, down to about -103 - and flag[u] is defined on what was WRITTEN:
+ *                 flag[u] = (some out[u][j] != 0).  A row whose logits all lie below -88.73 therefore is a zero row, flag 0.
  *   ens_merge   : anchor = (anchor * i + m[:, perm]) / (i + 1), the running mean of the Hungarian-matched query masks
  *                 (ensembler.py:86-98), in place, fp32 operations in that order
  *   ens_finish  : out[u, j] = anchor[u, keep[j]] * (argmax_c sem[sel[u], c] != 0) (matched-IoU filter of the queries and
@@ -509,6 +516,15 @@ int PH_FN(rowlist_pack)(const int32_t *pairs_in, const int32_t *pairs_out, const
  *                      output), 0 for an empty chain; coords[r] = (0, x, y, z) of sites[r] (int32 [v]: the kept site ids);
  *                      status bit 3 when a row is entirely zero (ME.to_sparse drops such a row: the caller must redo
  *                      the stage on its general path - the row count cannot change without a host read); c % 4 == 0
+ * Settled at the edges (tests/stage_edge_cases.py holds the library and the oracle to them):
+ *   - points_bounds clamps every coordinate to int32 first; n = 0 leaves the sentinels (INT_MAX x 3, INT_MIN x 3);
+ *   - a box holds at most 2^31 - 1 sites (site ids are int32): points_mark, points_link and cells_max refuse a larger one, or a
+ *     side <= 0, before any launch (non-zero return); mask_compact_rank with n = 0 writes n_keep = 0 and nothing else;
+ *   - cells_max takes the maximum BY VALUE, whatever the order of a chain: a NaN among a cell's points (either sign, any
+ *     payload) gives the quiet NaN 0x7FC00000; a maximum of zero is +0.0 when a +0.0 is among the cell's zeros and -0.0 when
+ *     they are all -0.0; -inf alone stays -inf; an empty cell is +0.0;
+ *   - a row is "entirely zero" when every channel compares equal to 0: a row of only -0.0 (written as -0.0) raises bit 3 as a
+ *     row of +0.0 does (ME.to_sparse tests != 0), a NaN or a denormal does not.
  * ------------------------------------------------------------------------------------------- */
 int PH_FN(points_bounds)(const int64_t *xyz, int64_t n, int32_t *out6, ph_stream_t stream);
 int PH_FN(points_mark)(const int64_t *xyz, int64_t n, const int32_t *h_lo3, const int32_t *h_dims3, uint8_t *flags,
@@ -527,16 +543,25 @@ int PH_FN(cells_max)(const float *h, int32_t c, const int32_t *head, const int32
  *   panop_queries  qp fp32 [q, c1] class probabilities (c1 = classes + dustbin, c1 <= 64) -> qtab int32 [4, 128]:
  *                  row 0 kidx[q'] = rank of query q' among the KEPT queries (arg-max class != 0, != dustbin, probability >
  *                  thr: helper.py:135-140; ascending query order) or -1, row 1 kq[k] = query of kept k, row 2 the arg-max
- *                  class of every query (first maximum), row 3 its probability (float bits); nk[0] = number kept
+ *                  class of every query (first maximum), row 3 its probability (float bits); nk[0] = number kept.  prob == thr
+ *                  is not kept.  For q < 128, rows 0 / 2 / 3 hold -1 / 0 / 0.0 at and beyond q; row 1 is written for the nk[0]
+ *                  kept queries only
  *   panop_argmax   masks fp32 [n, q] mask probabilities -> per voxel: winner = kept index with the largest prob x mask
- *                  (smallest index on ties; -1 when nothing is kept), own = mask of the winner >= occ_thr, conf = m_w /
+ *                  (the fp32 products p_k * m_k, each rounded once; smallest index on ties; a column that is not kept never
+ *                  wins, whatever it holds; -1 when nothing is kept), own = mask of the winner >= occ_thr, conf = m_w /
  *                  (sum_k m_k + 1e-8), vunc = max_k (p_k m_k) / sum_k (p_k m_k) (helper.py:150-153, 186, 199-206, 235-241);
- *                  areas int32 [2, 128] += (voxels won and owned by kept k, voxels with m_k >= occ_thr); caller zeroes
+ *                  areas int32 [2, 128] += (voxels won and owned by kept k, voxels with m_k >= occ_thr): the kernel ADDS to what
+ *                  the caller passes (zeros for one launch; a carry when the rows come in several launches).
+ *                  Nothing kept (K = 0): winner -1, own 0, conf 0, vunc 0, areas untouched.  A row whose kept products sum to
+ *                  0 (its kept masks are all 0): winner = kept index 0, conf = 0 / 1e-8 = 0, vunc = 0 / 0 = NaN as in the
+ *                  reference's formula; own is 0 there for every occ_thr > 0, so panop_write never moves that NaN into vox_unc
  *   panop_write    replays the reference's sequential walk over the kept queries (helper.py:188-250: mask_area /
  *                  original_area < overlap_thr skips, `thing_mask` bit c = class c is a thing, stuff segments of one class
  *                  merge and then write the panoptic id only) and writes per voxel panoptic id / semantic class /
  *                  ins_unc (query probability) / vox_conf / vox_unc; seg int32 [5, 128] (may be NULL): rows id, isthing,
- *                  category, query id of every segment, seg[4][0] = number of segments.  No host read anywhere.
+ *                  category, query id of every segment, seg[4][0] = number of segments (columns at and beyond that number
+ *                  are not written); n = 0 still writes the table.  (double)ma / oa < overlap_thr skips: a ratio exactly
+ *                  on the threshold (2 / 5 against 0.4) keeps the query.  winner must be -1 or below nk[0].  No host read.
  * ------------------------------------------------------------------------------------------- */
 int PH_FN(panop_queries)(const float *qp, int32_t q, int32_t c1, float thr, int32_t *qtab, int32_t *nk, ph_stream_t stream);
 int PH_FN(panop_argmax)(const float *masks, int64_t n, int32_t q, const int32_t *qtab, float occ_thr, int32_t *winner,

@@ -592,10 +592,36 @@ static int64_t pts_site(const int64_t *xyz, int64_t i, const int32_t *lo, const 
   return (x * dim[1] + y) * dim[2] + z;
 }
 
+/* 0 when the box has positive sides and at most 2^31 - 1 sites (site ids are int32) */
+static int pts_grid_bad(const int32_t *dim) {
+  int64_t vol = 1;
+  for (int a = 0; a < 3; ++a) {
+    if (dim[a] <= 0) return 1;
+    vol *= dim[a];
+    if (vol > 0x7FFFFFFF) return 1;
+  }
+  return 0;
+}
+
+/* order-preserving integer key of a float for the cell maximum (include/pasco_hip.h cells_max): -0.0 below +0.0, every NaN
+ * the one largest key */
+static int32_t cell_key(float x) {
+  int32_t i;
+  memcpy(&i, &x, 4);
+  return x != x ? INT_MAX : i ^ ((i >> 31) & 0x7fffffff);
+}
+
+static float cell_unkey(int32_t k) {
+  int32_t i = k == INT_MAX ? 0x7fc00000 : k ^ ((k >> 31) & 0x7fffffff);
+  float x;
+  memcpy(&x, &i, 4);
+  return x;
+}
+
 int pho_points_mark(const int64_t *xyz, int64_t n, const int32_t *h_lo3, const int32_t *h_dims3, uint8_t *flags,
                     int32_t *status, ph_stream_t stream) {
   (void)stream;
-  if (h_dims3[0] <= 0 || h_dims3[1] <= 0 || h_dims3[2] <= 0) return fail("points_mark: bad grid");
+  if (n < 0 || pts_grid_bad(h_dims3)) return fail("points_mark: bad grid (volume must stay below 2^31 sites)");
   for (int64_t i = 0; i < n; ++i) {
     int64_t s = pts_site(xyz, i, h_lo3, h_dims3);
     if (s >= 0) flags[s] = 1;
@@ -622,6 +648,7 @@ int pho_points_link(const int64_t *xyz, int64_t n, const int64_t *h_starts, int3
                     const int32_t *h_dims3, const int32_t *rank_of, int32_t *head, int32_t *next, ph_stream_t stream) {
   (void)stream;
   if (m < 1 || m > 8) return fail("points_link: needs 1 <= m <= 8");
+  if (pts_grid_bad(h_dims3)) return fail("points_link: bad grid");
   int b = 0;
   for (int64_t i = 0; i < n; ++i) {
     while (b + 1 < m && i >= h_starts[b + 1]) ++b;
@@ -642,15 +669,20 @@ int pho_cells_max(const float *h, int32_t c, const int32_t *head, const int32_t 
                   int32_t *status, ph_stream_t stream) {
   (void)stream;
   if (c <= 0 || c % 4 || m < 1 || m > 8) return fail("cells_max: needs c %% 4 == 0 and 1 <= m <= 8");
+  if (pts_grid_bad(h_dims3)) return fail("cells_max: bad grid");
   for (int64_t r = 0; r < v; ++r) {
     int nz = 0;
     for (int b = 0; b < m; ++b) {
       float *dst = out + (r * m + b) * c;
       int p = head[r * m + b];
-      for (int ch = 0; ch < c; ++ch) dst[ch] = p >= 0 ? h[(int64_t)p * c + ch] : 0.f;
-      for (p = p >= 0 ? next[p] : -1; p >= 0; p = next[p])
-        for (int ch = 0; ch < c; ++ch)
-          if (h[(int64_t)p * c + ch] > dst[ch]) dst[ch] = h[(int64_t)p * c + ch];
+      for (int ch = 0; ch < c; ++ch) {                   /* by value, whatever the chain's order: the max of the keys */
+        int32_t key = INT_MIN;
+        for (int q = p; q >= 0; q = next[q]) {
+          const int32_t kq = cell_key(h[(int64_t)q * c + ch]);
+          key = kq > key ? kq : key;
+        }
+        dst[ch] = p >= 0 ? cell_unkey(key) : 0.f;
+      }
       for (int ch = 0; ch < c; ++ch) nz |= dst[ch] != 0.f;
     }
     int s = sites[r];

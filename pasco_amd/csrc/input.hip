@@ -94,8 +94,9 @@ static int pts_grid(const int32_t *h_lo3, const int32_t *h_dims3, PtsGrid &g) {
     g.dim[a] = h_dims3[a];
     if (g.dim[a] <= 0) return 1;
     vol *= g.dim[a];
+    if (vol > 0x7FFFFFFF) return 1;      // site ids are int32: 2^31 - 1 sites at the most (tested per axis: no int64 wrap)
   }
-  return vol < 0x7FFFFFFF ? 0 : 1;
+  return 0;
 }
 
 __global__ void __launch_bounds__(256) k_pts_mark(const int64_t *__restrict__ xyz, int64_t n, PtsGrid g, uint8_t *__restrict__ flags,
@@ -164,6 +165,17 @@ extern "C" int ph_points_link(const int64_t *xyz, int64_t n, const int64_t *h_st
   return 0;
 }
 
+// Order-preserving integer key of a float for the cell maximum: k(a) < k(b) <=> a < b, -0.0 below +0.0, every NaN (either
+// sign, any payload) the one largest key.  The maximum of the keys is then independent of the order of a chain: a NaN in a
+// cell propagates as the quiet NaN 0x7FC00000, a zero maximum is +0.0 as soon as one +0.0 is among the maximal elements.
+__device__ __forceinline__ int cell_key(float x) {
+  const int i = __float_as_int(x);
+  return x != x ? INT_MAX : i ^ ((i >> 31) & 0x7fffffff);
+}
+__device__ __forceinline__ float cell_unkey(int k) {
+  return k == INT_MAX ? __int_as_float(0x7fc00000) : __int_as_float(k ^ ((k >> 31) & 0x7fffffff));
+}
+
 // ---- max over every cell's chain, merged row written once, coordinates, all-zero-row flag ------------------------------
 __global__ void __launch_bounds__(256) k_cells_max(const float *__restrict__ h, int c, const int32_t *__restrict__ head,
                                                    const int32_t *__restrict__ next, int64_t v, int m, const int32_t *__restrict__ sites,
@@ -180,14 +192,17 @@ __global__ void __launch_bounds__(256) k_cells_max(const float *__restrict__ h, 
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);       // no point of subnet b in this voxel: the dense detour holds 0
     int p = head[row * m + b];
     if (p >= 0) {
-      acc = *reinterpret_cast<const float4 *>(h + (int64_t)p * c + 4 * cq);
-      for (p = next[p]; p >= 0; p = next[p]) {
+      // the chain's order is the order the exchanges of k_pts_link landed in: the max runs on order-preserving integer keys
+      // (cell_key), so that NaN and the sign of a zero maximum do not depend on it (include/pasco_hip.h cells_max)
+      int kx = INT_MIN, ky = INT_MIN, kz = INT_MIN, kw = INT_MIN;
+      for (; p >= 0; p = next[p]) {
         const float4 x = *reinterpret_cast<const float4 *>(h + (int64_t)p * c + 4 * cq);
-        acc.x = x.x > acc.x ? x.x : acc.x;
-        acc.y = x.y > acc.y ? x.y : acc.y;
-        acc.z = x.z > acc.z ? x.z : acc.z;
-        acc.w = x.w > acc.w ? x.w : acc.w;
+        kx = max(kx, cell_key(x.x));
+        ky = max(ky, cell_key(x.y));
+        kz = max(kz, cell_key(x.z));
+        kw = max(kw, cell_key(x.w));
       }
+      acc = make_float4(cell_unkey(kx), cell_unkey(ky), cell_unkey(kz), cell_unkey(kw));
     }
     nz |= (acc.x != 0.f) | (acc.y != 0.f) | (acc.z != 0.f) | (acc.w != 0.f);
     *reinterpret_cast<float4 *>(out + (row * m + b) * c + 4 * cq) = acc;
