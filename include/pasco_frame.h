@@ -75,7 +75,7 @@ int PF_FN(points)(const float *pts, int64_t n_points, const pf_points_args *h_ar
 
 /* transform_coords (data/semantic_kitti.py) of n coordinates under M transforms (h_T fp32 [M, 4, 4], row major, host).
  * coords: fp64 [n, 3] (coords_int64 = 0) or int64 [n, 3] (coords_int64 = 1).  Rows i >= d_n[0] are skipped when d_n is
- * not null.  out int64 [M, n, 3]. */
+ * not null.  out int64 [M, n, 3].  Domain: results inside int32; the cast of a larger value is undefined. */
 int PF_FN(transform_coords)(const void *coords, int32_t coords_int64, int64_t n, const int64_t *d_n, const float *h_T,
                             int32_t M, int64_t *out, void *stream);
 

@@ -59,9 +59,17 @@ class LabelLib:
         sem = torch.empty(S, dtype=torch.uint8, device=raw.device)
         if status is None:
             status = torch.zeros(1, dtype=torch.int32, device=raw.device)
-        self._ok(self.lib.pl_semantic_grid(raw.data_ptr(), invalid.data_ptr(), lut.data_ptr(), int(lut.numel()), S,
-                                           sem.data_ptr(), status.data_ptr(), self._stream(raw)), "semantic_grid")
+        self.semantic_grid_into(raw, invalid, lut, sem, status)
         return sem, status
+
+    def semantic_grid_into(self, raw: torch.Tensor, invalid: torch.Tensor, lut: torch.Tensor, sem: torch.Tensor,
+                           status: torch.Tensor):
+        """`semantic_grid` into the caller's `sem` uint8 [S] and `status` int32 [1] (zeroed by the caller); any alignment."""
+        assert sem.is_cuda and sem.dtype == torch.uint8 and sem.is_contiguous() and sem.numel() == raw.numel()
+        assert status.is_cuda and status.dtype == torch.int32
+        self._ok(self.lib.pl_semantic_grid(raw.data_ptr(), invalid.data_ptr(), lut.data_ptr(), int(lut.numel()),
+                                           int(raw.numel()), sem.data_ptr(), status.data_ptr(), self._stream(raw)),
+                 "semantic_grid")
 
     def workspace_bytes(self, shape: Sequence[int], n_things: int) -> int:
         X, Y, Z = (int(v) for v in shape)
@@ -84,12 +92,24 @@ class LabelLib:
         out = torch.empty_like(sem)
         rec = torch.empty(RECORD, dtype=torch.int32, device=sem.device)
         sizes = torch.zeros(sizes_cap, dtype=torch.int32, device=sem.device) if sizes_cap > 0 else None
+        self.instances_into(sem, ids, min_size, ins, out, rec, sizes, sizes_cap, ws)
+        return ins, out, rec, sizes
+
+    def instances_into(self, sem: torch.Tensor, thing_ids: Sequence[int], min_size: int, instance: torch.Tensor,
+                       semantic_out: torch.Tensor, record: torch.Tensor, sizes: Optional[torch.Tensor], sizes_cap: int,
+                       ws: torch.Tensor):
+        """`instances` into the caller's tensors (any alignment but the workspace's 16 bytes): instance int32 [X, Y, Z],
+        semantic_out uint8 [X, Y, Z], record int32 [4], sizes int32 [>= sizes_cap] or None."""
+        ids = [int(t) for t in thing_ids]
+        assert instance.is_cuda and instance.dtype == torch.int32 and instance.is_contiguous() and instance.shape == sem.shape
+        assert semantic_out.is_cuda and semantic_out.dtype == torch.uint8 and semantic_out.is_contiguous()
+        assert semantic_out.shape == sem.shape and record.dtype == torch.int32 and record.numel() >= RECORD
+        assert sizes is None or (sizes.dtype == torch.int32 and sizes.numel() >= sizes_cap)
         X, Y, Z = (int(v) for v in sem.shape)
         self._ok(self.lib.pl_instances(sem.data_ptr(), X, Y, Z, (_i32 * max(len(ids), 1))(*ids), len(ids), int(min_size),
-                                       ins.data_ptr(), out.data_ptr(), rec.data_ptr(),
+                                       instance.data_ptr(), semantic_out.data_ptr(), record.data_ptr(),
                                        None if sizes is None else sizes.data_ptr(), int(sizes_cap), ws.data_ptr(),
                                        ws.numel(), self._stream(sem)), "instances")
-        return ins, out, rec, sizes
 
 
 _LIB = None

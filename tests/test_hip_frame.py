@@ -159,10 +159,11 @@ def test_transform_coords_both_paths_under_the_table():
 
 
 def test_label_bounds_match_build_item():
-    """Random grids, a grid without instances, a full-size 256 x 256 x 32 grid; two runs identical."""
+    """Random grids, a grid without instances, a full-size 256 x 256 x 32 grid; two runs identical.  Words 6..11 against the
+    host's bounds at the completion scale and as written (scale 1), words 0..5 against the host's box of the known sites."""
     cuda_only()
     from pasco_amd.data.frame_lib import BOUNDS, box_upper_bound, frame_lib
-    from pasco_amd.data.semantic_kitti import completion_bounds, transformed_labels
+    from pasco_amd.data.semantic_kitti import completion_bounds, transform_coords, transformed_labels
     rng = np.random.default_rng(4)
     cases = [small_labels(rng, (20, 24, 10)), small_labels(rng, (9, 31, 7)), small_labels(rng, (16, 16, 16), with_ins=False)]
     full_sem = np.zeros((256, 256, 32), np.uint8)
@@ -186,6 +187,11 @@ def test_label_bounds_match_build_item():
             dmin, dmax = completion_bounds(out[m, 6:9].clone(), out[m, 9:12].clone())
             assert torch.equal(dmin, min_c) and torch.equal(dmax, max_c), (ci, m, dmin, min_c, dmax, max_c)
             assert (out[m, :3] >= bb[m, :3]).all() and (out[m, 3:6] <= bb[m, 3:]).all()
+            # the twelve words as written: the raw minimum / maximum (scale 1 floors nothing) and the box itself
+            *_, raw_min, raw_max = transformed_labels(sem, ins, T, complete_scale=1)
+            assert torch.equal(out[m, 6:9], raw_min.int()) and torch.equal(out[m, 9:12], raw_max.int()), (ci, m, out[m], raw_min, raw_max)
+            to = transform_coords(torch.nonzero(torch.from_numpy(sem) != 255), T)
+            assert torch.equal(out[m, :3], to.min(0)[0]) and torch.equal(out[m, 3:6], to.max(0)[0]), (ci, m, out[m])
 
 
 def _k360_reader():
