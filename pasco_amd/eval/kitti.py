@@ -2,6 +2,7 @@
 
     python -m pasco_amd.eval.kitti --root <kitti root> --preprocess-root <preprocess root> --ckpt <model.ckpt> [--frames N]
                                    [--device-prep] [--instances-on-device --config <semantic-kitti.yaml>]
+                                   [--save-outputs DIR]
 
 Per frame: `FrameReader.batch` -> `net_from_checkpoint(...).step_inference` -> `SceneEvaluator.add` with the frame's
 `GroundTruth`.  Subnet transforms: subnet 0 sees the frame as it is, subnet i >= 1 under the fixed rotation / translation
@@ -13,6 +14,8 @@ is the measured mean wall time of `step_inference` in milliseconds (the referenc
 `--instances-on-device` builds the panoptic ground truth from the dataset's own `voxels/<frame>.label` / `.invalid` with the
 pl_* kernels (`data.instances`) instead of reading `instance_labels_v2/*.pkl`; frames are then listed from the dataset tree
 (`float(frame) % 5 == 0`, as the reference's generator selects them).
+`--save-outputs DIR` also writes `DIR/<frame>_<i>.pkl` for every output i of a frame (the subnets, then the ensemble) with the
+keys the reference's saving script writes; `python -m pasco_amd.viz` draws them.  Off by default; scoring is unchanged by it.
 """
 from __future__ import annotations
 
@@ -47,7 +50,8 @@ def frames_of(preprocess_root: str, sequence: str, root: str = None, frame_inter
 
 
 def evaluate(root: str, preprocess_root: str, ckpt: str, sequence: str = "08", frames: int = 0, device: str = "cuda",
-             device_prep: bool = False, instances: str = "file", config: str = None, grid=(256, 256, 32)):
+             device_prep: bool = False, instances: str = "file", config: str = None, grid=(256, 256, 32),
+             save_outputs: str = None):
     """-> (SceneEvaluator, mean step time in ms)."""
     dev = torch.device(device)
     net = net_from_checkpoint(ckpt, device=dev)
@@ -77,7 +81,11 @@ def evaluate(root: str, preprocess_root: str, ckpt: str, sequence: str = "08", f
                                                     b["min_Cs"], b["max_Cs"])
             torch.cuda.synchronize(dev)
             times.append(1e3 * (time.perf_counter() - t0))
-            ev.add(outs, sem_probs, GroundTruth.from_labels(sem, ins, net.thing_ids, device=dev))
+            gt = GroundTruth.from_labels(sem, ins, net.thing_ids, device=dev)
+            ev.add(outs, sem_probs, gt)
+            if save_outputs:
+                from ..viz.outputs import save_step_outputs
+                save_step_outputs(save_outputs, fid, outs, sem_probs, gt, sem, ins, xyz=b["xyz"][0] if "xyz" in b else None)
     return ev, float(np.mean(times))
 
 
@@ -93,12 +101,13 @@ def main(argv=None):
                     help="build the instance labels from the dataset's voxel files with the pl_* kernels (needs --config)")
     ap.add_argument("--config", help="the dataset's semantic-kitti.yaml (learning_map), for --instances-on-device")
     ap.add_argument("--grid", default="256,256,32", help="X,Y,Z of a voxel file, for --instances-on-device")
+    ap.add_argument("--save-outputs", metavar="DIR", help="also write <frame>_<i>.pkl per output, for python -m pasco_amd.viz")
     a = ap.parse_args(argv)
     if a.instances_on_device and not a.config:
         ap.error("--instances-on-device needs --config")
     ev, step_ms = evaluate(a.root, a.preprocess_root, a.ckpt, a.sequence, a.frames, device_prep=a.device_prep,
                            instances="device" if a.instances_on_device else "file", config=a.config,
-                           grid=tuple(int(v) for v in a.grid.split(",")))
+                           grid=tuple(int(v) for v in a.grid.split(",")), save_outputs=a.save_outputs)
     print(ev.tables(step_time=step_ms), end="")
 
 

@@ -2,7 +2,7 @@
 
     python -m pasco_amd.eval.kitti360 --root <KITTI-360 root> --preprocess-root <preprocess root> --label-root <SSCBench root>
                                       --match-file <kitti_360_match.txt> --ckpt <model.ckpt> [--split val|test] [--frames N]
-                                      [--host-prep] [--instances-on-device]
+                                      [--host-prep] [--instances-on-device] [--save-outputs DIR]
 
 Per frame: `Kitti360FrameReader.batch` -> `net_from_checkpoint(..., thing_ids=(1..6)).step_inference` -> `SceneEvaluator.add`
 with the frame's `GroundTruth`, under the 19 KITTI-360 class names.  Frames are prepared on the device by default (the pf_*
@@ -12,6 +12,7 @@ rotation of up to 10 degrees, a translation and flips per subnet and frame, so s
 draw.  The "inference time" column is the measured mean wall time of `step_inference` in milliseconds.
 `--instances-on-device` builds the panoptic ground truth from `<label-root>/labels/<seq>/<frame>_1_1.npy` with the pl_* kernels
 (`data.instances`) instead of reading `instance_labels_v2/*.pkl`.
+`--save-outputs DIR` also writes `DIR/<frame>_<i>.pkl` per output of a frame, as `eval.kitti` does; off by default.
 """
 from __future__ import annotations
 
@@ -29,7 +30,8 @@ from .metrics import SceneEvaluator
 
 
 def evaluate(root: str, preprocess_root: str, label_root: str, match_file: str, ckpt: str, split: str = "test",
-             frames: int = 0, device: str = "cuda", device_prep: bool = True, instances: str = "file"):
+             frames: int = 0, device: str = "cuda", device_prep: bool = True, instances: str = "file",
+             save_outputs: str = None):
     """-> (SceneEvaluator, mean step time in ms)."""
     dev = torch.device(device)
     net = net_from_checkpoint(ckpt, device=dev, thing_ids=THING_IDS)
@@ -57,7 +59,11 @@ def evaluate(root: str, preprocess_root: str, label_root: str, match_file: str, 
                                                     b["min_Cs"], b["max_Cs"])
             torch.cuda.synchronize(dev)
             times.append(1e3 * (time.perf_counter() - t0))
-            ev.add(outs, sem_probs, GroundTruth.from_labels(sem, ins, net.thing_ids, device=dev))
+            gt = GroundTruth.from_labels(sem, ins, net.thing_ids, device=dev)
+            ev.add(outs, sem_probs, gt)
+            if save_outputs:
+                from ..viz.outputs import save_step_outputs
+                save_step_outputs(save_outputs, fid, outs, sem_probs, gt, sem, ins, xyz=b["xyz"][0] if "xyz" in b else None)
     return ev, float(np.mean(times))
 
 
@@ -73,9 +79,11 @@ def main(argv=None):
     ap.add_argument("--host-prep", action="store_true", help="prepare frames on the host instead of with the pf_* kernels")
     ap.add_argument("--instances-on-device", action="store_true",
                     help="build the instance labels from the label .npy files with the pl_* kernels")
+    ap.add_argument("--save-outputs", metavar="DIR", help="also write <frame>_<i>.pkl per output, for python -m pasco_amd.viz")
     a = ap.parse_args(argv)
     ev, step_ms = evaluate(a.root, a.preprocess_root, a.label_root, a.match_file, a.ckpt, a.split, a.frames,
-                           device_prep=not a.host_prep, instances="device" if a.instances_on_device else "file")
+                           device_prep=not a.host_prep, instances="device" if a.instances_on_device else "file",
+                           save_outputs=a.save_outputs)
     print(ev.tables(step_time=step_ms), end="")
 
 
