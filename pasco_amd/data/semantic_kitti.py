@@ -85,15 +85,20 @@ def read_waffleiron_features(path: str, embedding_index: Optional[int] = None,
                              rng: Optional[np.random.Generator] = None):
     """seg_feats_tta/*.pkl -> (xyz [P,3], vote [P,V], intensity [P,1], embedding [P,256]) (kitti_dataset.py:290-303).
     The file holds E test-time-augmented embeddings; the reference draws one at random per call - pass
-    `embedding_index` for a reproducible choice, or an `rng`."""
-    with open(path, "rb") as f:
-        data = pickle.load(f)
+    `embedding_index` for a reproducible choice, or an `rng`.  `path` may be the already loaded dictionary (the three
+    arrays computed by `pasco_amd.waffle.Extractor` instead of read from a file)."""
+    data = path if isinstance(path, dict) else _load_pickle(path)
     emb = data["embedding"]
     if embedding_index is None:
         embedding_index = int((rng or np.random.default_rng()).integers(0, emb.shape[0]))
     embedding = emb[embedding_index].T
     xyz_density = data["coords"]
     return xyz_density[:, :3], data["vote"], xyz_density[:, 3:], embedding
+
+
+def _load_pickle(path: str):
+    with open(path, "rb") as f:
+        return pickle.load(f)
 
 
 def read_instance_label_pickle(path: str):
@@ -230,11 +235,14 @@ class FrameReader:
         <root>/dataset/sequences/<seq>/labels/<frame>.label
         <preprocess_root>/instance_labels_v2/<seq>/<frame>_1_1.pkl
         <preprocess_root>/waffleiron_v2/sequences/<seq>/seg_feats_tta/<frame>.pkl
+    With `features=` a `pasco_amd.waffle.Extractor` the last file is not read: its three arrays are computed from
+    `<root>/dataset/sequences/<seq>/velodyne/<frame>.bin`.
     `batch(seq, frame, Ts)` returns the collated a0 contract for len(Ts) subnets (the reference's validation loader
     feeds every subnet the same frame under its own transform)."""
 
     def __init__(self, root: str, preprocess_root: str, complete_scale: int = 8, instances: str = "file",
-                 config: Optional[str] = None, grid=(256, 256, 32), thing_ids=(1, 2, 3, 4, 5, 6, 7, 8), label_device="cuda"):
+                 config: Optional[str] = None, grid=(256, 256, 32), thing_ids=(1, 2, 3, 4, 5, 6, 7, 8), label_device="cuda",
+                 features=None):
         """`instances="file"` reads the label grids from the instance pickle; `"device"` builds them from the dataset's own
         `voxels/<frame>.label` / `.invalid` with the pl_* kernels on `label_device` (`data.instances`; `config` is the
         dataset's semantic-kitti.yaml), so no instance_labels_v2 directory is needed."""
@@ -245,6 +253,7 @@ class FrameReader:
         self.root, self.preprocess_root, self.complete_scale = root, preprocess_root, complete_scale
         self.instances, self.grid, self.thing_ids, self.label_device = instances, tuple(grid), tuple(thing_ids), label_device
         self._lut, self._config, self._last = None, config, (None, None)
+        self.features = features
 
     def paths(self, sequence: str, frame_id: str):
         return (os.path.join(self.preprocess_root, "instance_labels_v2", sequence, f"{frame_id}_1_1.pkl"),
@@ -275,6 +284,9 @@ class FrameReader:
         """`device=None` (or a CPU device) runs the host restatement `build_item`; a GPU device runs the same preparation
         through the pf_* kernels (`data.device_prep`), bit-equal, with the batch's tensors left on that device."""
         _, feats, pts = self.paths(sequence, frame_id)
+        if self.features is not None:
+            scan = read_pointcloud(os.path.join(self.root, "dataset", "sequences", sequence, "velodyne", f"{frame_id}.bin"))
+            feats = self.features.frame(scan, int(frame_id))
         sem, ins = self.labels(sequence, frame_id)
         if device is not None and torch.device(device).type == "cuda":
             plab = read_point_instance_labels(pts) if os.path.exists(pts) else None
@@ -292,8 +304,7 @@ def prepare_semantic_kitti_on_device(feats_path: str, semantic_label: np.ndarray
     are stored (the embedding as [256, P], read transposed by the kernel) - no host-side concatenation."""
     from . import device_prep as DP
     from .frame_lib import _seg, segment
-    with open(feats_path, "rb") as f:
-        data = pickle.load(f)
+    data = feats_path if isinstance(feats_path, dict) else _load_pickle(feats_path)
     pts = DP.upload(np.ascontiguousarray(data["coords"]), device)
     vote = DP.upload(np.ascontiguousarray(data["vote"]), device).contiguous()
     emb = DP.upload(np.ascontiguousarray(data["embedding"][embedding_index]), device).contiguous()    # [256, P]

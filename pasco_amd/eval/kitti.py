@@ -3,6 +3,7 @@
     python -m pasco_amd.eval.kitti --root <kitti root> --preprocess-root <preprocess root> --ckpt <model.ckpt> [--frames N]
                                    [--device-prep] [--instances-on-device --config <semantic-kitti.yaml>]
                                    [--save-outputs DIR]
+                                   [--features-on-device --waffle-ckpt <ckpt_last.pth> --waffle-config <yaml> [--num-votes V]]
 
 Per frame: `FrameReader.batch` -> `net_from_checkpoint(...).step_inference` -> `SceneEvaluator.add` with the frame's
 `GroundTruth`.  Subnet transforms: subnet 0 sees the frame as it is, subnet i >= 1 under the fixed rotation / translation
@@ -16,6 +17,8 @@ pl_* kernels (`data.instances`) instead of reading `instance_labels_v2/*.pkl`; f
 (`float(frame) % 5 == 0`, as the reference's generator selects them).
 `--save-outputs DIR` also writes `DIR/<frame>_<i>.pkl` for every output i of a frame (the subnets, then the ensemble) with the
 keys the reference's saving script writes; `python -m pasco_amd.viz` draws them.  Off by default; scoring is unchanged by it.
+`--features-on-device` computes the WaffleIron point features of every frame from `velodyne/<frame>.bin` with the pw_* kernels
+(`pasco_amd.waffle`) instead of reading `waffleiron_v2/.../seg_feats_tta/<frame>.pkl`: no waffleiron_v2 folder is needed.
 """
 from __future__ import annotations
 
@@ -51,16 +54,25 @@ def frames_of(preprocess_root: str, sequence: str, root: str = None, frame_inter
 
 def evaluate(root: str, preprocess_root: str, ckpt: str, sequence: str = "08", frames: int = 0, device: str = "cuda",
              device_prep: bool = False, instances: str = "file", config: str = None, grid=(256, 256, 32),
-             save_outputs: str = None):
+             save_outputs: str = None, features: str = "file", waffle_ckpt: str = None, waffle_config: str = None,
+             num_votes: int = 10):
     """-> (SceneEvaluator, mean step time in ms)."""
     dev = torch.device(device)
     net = net_from_checkpoint(ckpt, device=dev)
+    extractor = None
+    if features == "device":
+        if not (waffle_ckpt and waffle_config):
+            raise ValueError("features='device' needs the WaffleIron checkpoint and its yaml (waffle_ckpt=, waffle_config=)")
+        from ..waffle import Extractor
+        extractor = Extractor(waffle_ckpt, waffle_config, dev, num_votes=num_votes)
+    elif features != "file":
+        raise ValueError(f"features={features!r}: 'file' or 'device'")
     if instances == "device":
         reader = FrameReader(root, preprocess_root, instances="device", config=config, grid=grid,
-                             thing_ids=net.thing_ids, label_device=dev)
+                             thing_ids=net.thing_ids, label_device=dev, features=extractor)
         ids = frames_of(preprocess_root, sequence, root=root)
     else:
-        reader = FrameReader(root, preprocess_root)
+        reader = FrameReader(root, preprocess_root, features=extractor)
         ids = frames_of(preprocess_root, sequence)
     if frames:
         ids = ids[:frames]
@@ -102,12 +114,21 @@ def main(argv=None):
     ap.add_argument("--config", help="the dataset's semantic-kitti.yaml (learning_map), for --instances-on-device")
     ap.add_argument("--grid", default="256,256,32", help="X,Y,Z of a voxel file, for --instances-on-device")
     ap.add_argument("--save-outputs", metavar="DIR", help="also write <frame>_<i>.pkl per output, for python -m pasco_amd.viz")
+    ap.add_argument("--features-on-device", action="store_true",
+                    help="compute the WaffleIron point features from velodyne/ with the pw_* kernels (needs --waffle-ckpt, --waffle-config)")
+    ap.add_argument("--waffle-ckpt", help="the WaffleIron checkpoint (ckpt_last.pth), for --features-on-device")
+    ap.add_argument("--waffle-config", help="the WaffleIron yaml, for --features-on-device")
+    ap.add_argument("--num-votes", type=int, default=10, help="test-time augmentations per frame, for --features-on-device")
     a = ap.parse_args(argv)
     if a.instances_on_device and not a.config:
         ap.error("--instances-on-device needs --config")
+    if a.features_on_device and not (a.waffle_ckpt and a.waffle_config):
+        ap.error("--features-on-device needs --waffle-ckpt and --waffle-config")
     ev, step_ms = evaluate(a.root, a.preprocess_root, a.ckpt, a.sequence, a.frames, device_prep=a.device_prep,
                            instances="device" if a.instances_on_device else "file", config=a.config,
-                           grid=tuple(int(v) for v in a.grid.split(",")), save_outputs=a.save_outputs)
+                           grid=tuple(int(v) for v in a.grid.split(",")), save_outputs=a.save_outputs,
+                           features="device" if a.features_on_device else "file", waffle_ckpt=a.waffle_ckpt,
+                           waffle_config=a.waffle_config, num_votes=a.num_votes)
     print(ev.tables(step_time=step_ms), end="")
 
 
