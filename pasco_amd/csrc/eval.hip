@@ -11,29 +11,12 @@
 // depend on their order either.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/pasco_eval.h"
+#include "side_common.h"
 
 namespace {
-
-thread_local char g_err[512];
-
-int fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return 1;
-}
-
-#define PE_CHECK_HIP(expr)                                                                      \
-  do {                                                                                          \
-    hipError_t _e = (expr);                                                                     \
-    if (_e != hipSuccess) return fail("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int BLOCK = 256;
 constexpr int NB = PE_BINS;
@@ -280,9 +263,7 @@ Edges edges_from(const float *h) {
 
 extern "C" {
 
-int pe_abi_version(void) { return PE_ABI_VERSION; }
-
-const char *pe_last_error(void) { return g_err; }
+SIDE_EXPORTS(PE_FN, PE_ABI_VERSION)
 
 int64_t pe_ssc_workspace_bytes(int64_t n_sites, int32_t c) {
   return (int64_t)blocks_for(n_sites) * ssc_slab(c) * (int64_t)sizeof(long long);
@@ -299,10 +280,10 @@ int pe_ssc(const float *probs, const float *conf, const uint8_t *gt, int64_t n_s
   const int nb = blocks_for(n_sites), slab = ssc_slab(c);
   hipLaunchKernelGGL(k_ssc, dim3(nb), dim3(BLOCK), 0, st, probs, conf, gt, n_sites, c, edges_from(h_edges),
                      static_cast<long long *>(ws));
-  PE_CHECK_HIP(hipGetLastError());
+  SIDE_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_reduce, dim3((slab + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, static_cast<const long long *>(ws), nb,
                      slab, PE_SSC_COUNTS(c), 2 * NB, 1.0 / CONF_SCALE, 1.0 / NLL_SCALE, counts, sums);
-  PE_CHECK_HIP(hipGetLastError());
+  SIDE_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
@@ -312,12 +293,12 @@ int pe_panop_pairs(const int64_t *site, const int32_t *pred, int64_t n, const ui
   if (n_gt < 0 || n_gt > PE_MAX_GT) return fail("pe_panop_pairs: gt id %d beyond %d", n_gt, PE_MAX_GT);
   if (n < 0) return fail("pe_panop_pairs: %lld rows", (long long)n);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  PE_CHECK_HIP(hipMemsetAsync(area, 0, sizeof(int64_t) * (n_pred + 1), st));
-  PE_CHECK_HIP(hipMemsetAsync(inter, 0, sizeof(int64_t) * (int64_t)(n_gt + 1) * (n_pred + 1), st));
+  SIDE_CHECK_HIP(hipMemsetAsync(area, 0, sizeof(int64_t) * (n_pred + 1), st));
+  SIDE_CHECK_HIP(hipMemsetAsync(inter, 0, sizeof(int64_t) * (int64_t)(n_gt + 1) * (n_pred + 1), st));
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_panop_pairs, dim3(blocks_for(n)), dim3(BLOCK), 0, st, site, pred, n, gt_sem, gt_id, n_sites, n_pred,
                      n_gt, reinterpret_cast<unsigned long long *>(area), reinterpret_cast<unsigned long long *>(inter));
-  PE_CHECK_HIP(hipGetLastError());
+  SIDE_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
@@ -327,7 +308,7 @@ int pe_match(const int64_t *area, const int64_t *gt_area, const int64_t *inter, 
   if (n_gt < 0 || n_gt > PE_MAX_GT) return fail("pe_match: gt id %d beyond %d", n_gt, PE_MAX_GT);
   hipLaunchKernelGGL(k_match, dim3(1), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), area, gt_area, inter, n_pred, n_gt,
                      map);
-  PE_CHECK_HIP(hipGetLastError());
+  SIDE_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
@@ -341,10 +322,10 @@ int pe_mask_ece(const int64_t *site, const int32_t *pred, const float *conf, int
   const int nb = blocks_for(n);
   hipLaunchKernelGGL(k_mask_ece, dim3(nb), dim3(BLOCK), 0, st, site, pred, conf, n, gt_id, n_sites, map, n_pred,
                      edges_from(h_edges), static_cast<long long *>(ws));
-  PE_CHECK_HIP(hipGetLastError());
+  SIDE_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_reduce, dim3(1), dim3(BLOCK), 0, st, static_cast<const long long *>(ws), nb, ECE_SLAB, PE_ECE_COUNTS,
                      NB, 1.0 / CONF_SCALE, 1.0 / CONF_SCALE, counts, sums);
-  PE_CHECK_HIP(hipGetLastError());
+  SIDE_CHECK_HIP(hipGetLastError());
   return 0;
 }
 

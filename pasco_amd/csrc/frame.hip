@@ -9,31 +9,14 @@
 // value: min / max are order independent, so results are identical from run to run.  No float atomics.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/pasco_frame.h"
+#include "side_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-thread_local char g_err[512];
-
-int fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return 1;
-}
-
-#define PF_CHECK_LAUNCH(what)                                                                         \
-  do {                                                                                                \
-    hipError_t _e = hipGetLastError();                                                                \
-    if (_e != hipSuccess) return fail("%s:%d: %s -> %s", __FILE__, __LINE__, what, hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;
@@ -365,9 +348,7 @@ int grid_for(int64_t work) {
 
 extern "C" {
 
-int PF_FN(abi_version)(void) { return PF_ABI_VERSION; }
-
-const char *PF_FN(last_error)(void) { return g_err; }
+SIDE_EXPORTS(PF_FN, PF_ABI_VERSION)
 
 int32_t PF_FN(points_channels)(const pf_points_args *a) {
   int32_t c = 7;
@@ -395,9 +376,9 @@ int PF_FN(points)(const float *pts, int64_t n, const pf_points_args *h_args, flo
   int *counts = static_cast<int *>(ws);
   const int C = PF_FN(points_channels)(h_args);
   hipLaunchKernelGGL(k_count, dim3(nb), dim3(BLOCK), 0, st, pts, n, a, counts);
-  PF_CHECK_LAUNCH("k_count");
+  SIDE_CHECK_LAUNCH("k_count");
   hipLaunchKernelGGL(k_points, dim3(nb), dim3(BLOCK), 0, st, pts, n, a, C, counts, feat, voxel, src, d_kept);
-  PF_CHECK_LAUNCH("k_points");
+  SIDE_CHECK_LAUNCH("k_points");
   return 0;
 }
 
@@ -416,7 +397,7 @@ int PF_FN(transform_coords)(const void *coords, int32_t coords_int64, int64_t n,
     hipLaunchKernelGGL(k_transform<true>, dim3(grid_for(n)), dim3(BLOCK), 0, st, coords, n, d_n, T, M, out);
   else
     hipLaunchKernelGGL(k_transform<false>, dim3(grid_for(n)), dim3(BLOCK), 0, st, coords, n, d_n, T, M, out);
-  PF_CHECK_LAUNCH("k_transform");
+  SIDE_CHECK_LAUNCH("k_transform");
   return 0;
 }
 
@@ -447,12 +428,12 @@ int PF_FN(label_bounds)(const uint8_t *sem, const uint8_t *ins, int32_t X, int32
   hipStream_t st = static_cast<hipStream_t>(stream);
   int32_t *flag = static_cast<int32_t *>(ws);
   hipLaunchKernelGGL(k_bounds_init, dim3(1), dim3(BLOCK), 0, st, out, M, flag);
-  PF_CHECK_LAUNCH("k_bounds_init");
+  SIDE_CHECK_LAUNCH("k_bounds_init");
   const int64_t S = (int64_t)X * Y * Z;
   hipLaunchKernelGGL(k_bounds_box, dim3(grid_for(S), M), dim3(BLOCK), 0, st, sem, ins, X, Y, Z, T, M, out, flag);
-  PF_CHECK_LAUNCH("k_bounds_box");
+  SIDE_CHECK_LAUNCH("k_bounds_box");
   hipLaunchKernelGGL(k_bounds_samples, dim3(grid_for(vmax), M), dim3(BLOCK), 0, st, sem, ins, X, Y, Z, Ti, M, out, flag);
-  PF_CHECK_LAUNCH("k_bounds_samples");
+  SIDE_CHECK_LAUNCH("k_bounds_samples");
   return 0;
 }
 

@@ -26,29 +26,12 @@
 // A stale read of a parent (another CU's L1) is an older ancestor of the same set, which both loops tolerate; the atomic
 // itself returns the true word.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/pasco_label.h"
+#include "side_common.h"
 
 namespace {
-
-thread_local char g_err[512];
-
-int fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return 1;
-}
-
-#define PL_CHECK_LAUNCH(what)                                                                         \
-  do {                                                                                                \
-    hipError_t _e = hipGetLastError();                                                                \
-    if (_e != hipSuccess) return fail("%s:%d: %s -> %s", __FILE__, __LINE__, what, hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;
@@ -448,9 +431,7 @@ bool grid_ok(int32_t X, int32_t Y, int32_t Z) {
 
 extern "C" {
 
-int PL_FN(abi_version)(void) { return PL_ABI_VERSION; }
-
-const char *PL_FN(last_error)(void) { return g_err; }
+SIDE_EXPORTS(PL_FN, PL_ABI_VERSION)
 
 int PL_FN(semantic_grid)(const uint16_t *raw, const uint8_t *invalid, const uint8_t *lut, int32_t n_lut, int64_t S,
                          uint8_t *sem, int32_t *d_status, void *stream) {
@@ -467,7 +448,7 @@ int PL_FN(semantic_grid)(const uint16_t *raw, const uint8_t *invalid, const uint
   } else {
     k_semantic<false><<<static_cast<unsigned>(blocks), BLOCK, 0, st>>>(raw, invalid, lut, n_lut, n_bytes, sem, d_status);
   }
-  PL_CHECK_LAUNCH("k_semantic");
+  SIDE_CHECK_LAUNCH("k_semantic");
   return 0;
 }
 
@@ -514,17 +495,17 @@ int PL_FN(instances)(const uint8_t *sem, int32_t X, int32_t Y, int32_t Z, const 
 
   k_local<<<static_cast<unsigned>(tiles), BLOCK, 0, st>>>(sem, g, tab, tiles_y, tiles_z,
                                                           reinterpret_cast<uintptr_t>(sem) % 8 == 0, parent, count, record);
-  PL_CHECK_LAUNCH("k_local");
+  SIDE_CHECK_LAUNCH("k_local");
   k_merge<<<nb, BLOCK, 0, st>>>(sem, g, tab, S, parent, record);
-  PL_CHECK_LAUNCH("k_merge");
+  SIDE_CHECK_LAUNCH("k_merge");
   k_flatten<<<nb, BLOCK, 0, st>>>(S, parent, count);
-  PL_CHECK_LAUNCH("k_flatten");
+  SIDE_CHECK_LAUNCH("k_flatten");
   k_blockcnt<<<nb, BLOCK, 0, st>>>(sem, tab, S, nt, min_size, parent, count, table, record);
-  PL_CHECK_LAUNCH("k_blockcnt");
+  SIDE_CHECK_LAUNCH("k_blockcnt");
   k_scan<<<1, SCAN_BLOCK, 0, st>>>(table, static_cast<int64_t>(nt) * nb, record);
-  PL_CHECK_LAUNCH("k_scan");
+  SIDE_CHECK_LAUNCH("k_scan");
   k_rank<<<nb, BLOCK, 0, st>>>(sem, tab, S, min_size, parent, count, table, sizes, sizes_cap);
-  PL_CHECK_LAUNCH("k_rank");
+  SIDE_CHECK_LAUNCH("k_rank");
   const bool vec = S % 4 == 0 && reinterpret_cast<uintptr_t>(sem) % 4 == 0 &&
                    reinterpret_cast<uintptr_t>(semantic_out) % 4 == 0 && reinterpret_cast<uintptr_t>(instance) % 16 == 0;
   if (vec) {
@@ -532,7 +513,7 @@ int PL_FN(instances)(const uint8_t *sem, int32_t X, int32_t Y, int32_t Z, const 
   } else {
     k_write<1><<<nb, BLOCK, 0, st>>>(sem, tab, S, parent, count, instance, semantic_out);
   }
-  PL_CHECK_LAUNCH("k_write");
+  SIDE_CHECK_LAUNCH("k_write");
   return 0;
 }
 

@@ -17,31 +17,14 @@
 //
 // Why every loop ends: each turn of the walk takes either a voxel step or a brick step and both counters carry a hard cap.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/pasco_view.h"
+#include "side_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-thread_local char g_err[512];
-
-int fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return 1;
-}
-
-#define PV_CHECK_LAUNCH(what)                                                                         \
-  do {                                                                                                \
-    hipError_t _e = hipGetLastError();                                                                \
-    if (_e != hipSuccess) return fail("%s:%d: %s -> %s", __FILE__, __LINE__, what, hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;
@@ -419,8 +402,7 @@ inline hipStream_t S(void *stream) { return static_cast<hipStream_t>(stream); }
 
 extern "C" {
 
-int PV_FN(abi_version)(void) { return PV_ABI_VERSION; }
-const char *PV_FN(last_error)(void) { return g_err; }
+SIDE_EXPORTS(PV_FN, PV_ABI_VERSION)
 
 int PV_FN(majority_pool)(const uint8_t *grid, int32_t X, int32_t Y, int32_t Z, int32_t k, uint8_t *out, int32_t *d_status,
                          void *stream) {
@@ -431,7 +413,7 @@ int PV_FN(majority_pool)(const uint8_t *grid, int32_t X, int32_t Y, int32_t Z, i
   const int cells = o.X * o.Y * o.Z;
   if (cells == 0) return 0;
   k_pool<<<blocks_for(cells), BLOCK, 0, S(stream)>>>(grid, Grid{X, Y, Z}, k, o, cells, out, d_status);
-  PV_CHECK_LAUNCH("k_pool");
+  SIDE_CHECK_LAUNCH("k_pool");
   return 0;
 }
 
@@ -446,7 +428,7 @@ int PV_FN(window_filter)(const float *in, const uint8_t *mask, int32_t X, int32_
   else if (op == PV_OP_MAX) k_filter<PV_OP_MAX><<<nblk, BLOCK, 0, S(stream)>>>(in, mask, g, sites, out);
   else if (op == PV_OP_AVG) k_filter<PV_OP_AVG><<<nblk, BLOCK, 0, S(stream)>>>(in, mask, g, sites, out);
   else return fail("pv_window_filter: op = %d", op);
-  PV_CHECK_LAUNCH("k_filter");
+  SIDE_CHECK_LAUNCH("k_filter");
   return 0;
 }
 
@@ -461,7 +443,7 @@ int PV_FN(compose)(const int32_t *panoptic, const int32_t *seg, int32_t n_seg, c
     return fail("pv_compose: view %d misses an input", view);
   const int sites = X * Y * Z;
   k_compose<<<blocks_for(sites), BLOCK, 0, S(stream)>>>(panoptic, seg, n_seg, sem, conf, sites, view, vmin, vmax, out);
-  PV_CHECK_LAUNCH("k_compose");
+  SIDE_CHECK_LAUNCH("k_compose");
   return 0;
 }
 
@@ -477,7 +459,7 @@ int PV_FN(bricks)(const uint32_t *colour, int32_t X, int32_t Y, int32_t Z, uint3
   const Grid nb{(X + B - 1) / B, (Y + B - 1) / B, (Z + B - 1) / B};
   const int n_bricks = nb.X * nb.Y * nb.Z;
   k_bricks<<<static_cast<unsigned>((n_bricks + 31) / 32), BLOCK, 0, S(stream)>>>(colour, Grid{X, Y, Z}, nb, n_bricks, bits);
-  PV_CHECK_LAUNCH("k_bricks");
+  SIDE_CHECK_LAUNCH("k_bricks");
   return 0;
 }
 
@@ -498,7 +480,7 @@ int PV_FN(render)(const uint32_t *colour, const uint32_t *bits, int32_t X, int32
   const dim3 grid(static_cast<unsigned>((W + 15) / 16), static_cast<unsigned>((H + 15) / 16));
   k_render<<<grid, BLOCK, 0, S(stream)>>>(colour, bits, Grid{X, Y, Z}, nb, cam, W, H, palette, n_palette, fx, fy, fz,
                                           background, cap_fine, cap_coarse, hit, face, rgb, d_status);
-  PV_CHECK_LAUNCH("k_render");
+  SIDE_CHECK_LAUNCH("k_render");
   return 0;
 }
 
@@ -508,7 +490,7 @@ int PV_FN(downsample)(const uint8_t *in, int32_t W, int32_t H, int32_t s, uint8_
   if (!in || !out) return fail("pv_downsample: null pointer");
   const int n_out = W * H * 3;
   k_downsample<<<blocks_for(n_out), BLOCK, 0, S(stream)>>>(in, W, s, n_out, out);
-  PV_CHECK_LAUNCH("k_downsample");
+  SIDE_CHECK_LAUNCH("k_downsample");
   return 0;
 }
 

@@ -18,31 +18,14 @@
 // Why every loop ends: shells run r = 0 .. max(G) - 1, a shell's loops run over the clipped cube, a cell's loop over its CSR
 // range clipped to [0, n), the list insertion over k entries, the binary search over 32 halvings.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/pasco_waffle.h"
+#include "side_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-thread_local char g_err[512];
-
-int fail(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return 1;
-}
-
-#define PW_CHECK_LAUNCH(what)                                                                         \
-  do {                                                                                                \
-    hipError_t _e = hipGetLastError();                                                                \
-    if (_e != hipSuccess) return fail("%s:%d: %s -> %s", __FILE__, __LINE__, what, hipGetErrorString(_e)); \
-  } while (0)
 
 constexpr int BLOCK = 256;
 constexpr int SEARCH_BLOCK = 128;
@@ -456,9 +439,7 @@ Cells make_cells(double lox, double loy, double loz, double h, int32_t gx, int32
 
 extern "C" {
 
-int PW_FN(abi_version)(void) { return PW_ABI_VERSION; }
-
-const char *PW_FN(last_error)(void) { return g_err; }
+SIDE_EXPORTS(PW_FN, PW_ABI_VERSION)
 
 int PW_FN(voxel_keys)(const float *pc, int32_t ld, int64_t n, const float *mn, float voxel, int32_t *key, int32_t *d_status,
                       void *stream) {
@@ -467,7 +448,7 @@ int PW_FN(voxel_keys)(const float *pc, int32_t ld, int64_t n, const float *mn, f
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_voxel_keys, dim3(blocks_for(n * 3)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), pc, ld, n, mn,
                      voxel, key, d_status);
-  PW_CHECK_LAUNCH("k_voxel_keys");
+  SIDE_CHECK_LAUNCH("k_voxel_keys");
   return 0;
 }
 
@@ -481,7 +462,7 @@ int PW_FN(cell_index)(const float *pc, int32_t ld, int64_t n, int32_t d0, int32_
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_cell_index, dim3(blocks_for(n)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), pc, ld, n, d0, d1,
                      lo0, lo1, res0, res1, H, W, cell, d_status);
-  PW_CHECK_LAUNCH("k_cell_index");
+  SIDE_CHECK_LAUNCH("k_cell_index");
   return 0;
 }
 
@@ -493,7 +474,7 @@ int PW_FN(grid_cells)(const float *xyz, int32_t ld, int64_t n, double lox, doubl
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_grid_cells, dim3(blocks_for(n)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), xyz, ld, n, c, cell,
                      d_status);
-  PW_CHECK_LAUNCH("k_grid_cells");
+  SIDE_CHECK_LAUNCH("k_grid_cells");
   return 0;
 }
 
@@ -505,7 +486,7 @@ int PW_FN(cells_build)(const int32_t *cell, const int32_t *order, int64_t n, int
   const int64_t threads = n > ncell + 1 ? n : ncell + 1;
   hipLaunchKernelGGL(k_cells_build, dim3(blocks_for(threads)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), cell, order,
                      static_cast<int>(n), ncell, start, d_status);
-  PW_CHECK_LAUNCH("k_cells_build");
+  SIDE_CHECK_LAUNCH("k_cells_build");
   return 0;
 }
 
@@ -519,7 +500,7 @@ int PW_FN(knn)(const float *xyz, int32_t ld, int64_t n, const int32_t *start, co
   hipLaunchKernelGGL(k_search<true>, dim3(blocks_for(n, SEARCH_BLOCK)), dim3(SEARCH_BLOCK), 0,
                      static_cast<hipStream_t>(stream), xyz, ld, static_cast<int>(n), start, order, c, xyz, ld,
                      static_cast<int>(n), k, out);
-  PW_CHECK_LAUNCH("k_search<knn>");
+  SIDE_CHECK_LAUNCH("k_search<knn>");
   return 0;
 }
 
@@ -535,7 +516,7 @@ int PW_FN(nearest)(const float *xyz, int32_t ld, int64_t n, const int32_t *start
   hipLaunchKernelGGL(k_search<false>, dim3(blocks_for(m, SEARCH_BLOCK)), dim3(SEARCH_BLOCK), 0,
                      static_cast<hipStream_t>(stream), xyz, ld, static_cast<int>(n), start, order, c, q, ldq,
                      static_cast<int>(m), 1, out);
-  PW_CHECK_LAUNCH("k_search<nearest>");
+  SIDE_CHECK_LAUNCH("k_search<nearest>");
   return 0;
 }
 
@@ -551,7 +532,7 @@ int PW_FN(flatten)(const float *tokens, int64_t n, int32_t C, const float *scale
   else
     hipLaunchKernelGGL(k_flatten<1>, dim3(blocks_for(static_cast<int64_t>(ncell) * C)), dim3(BLOCK), 0, st_, tokens,
                        static_cast<int>(n), C, scale, shift, start, order, ncell, grid, d_status);
-  PW_CHECK_LAUNCH("k_flatten");
+  SIDE_CHECK_LAUNCH("k_flatten");
   return 0;
 }
 
@@ -568,7 +549,7 @@ int PW_FN(dwconv3x3)(const float *in, int32_t H, int32_t W, int32_t C, const flo
   else if (relu) hipLaunchKernelGGL((k_dwconv<true, 1>), g, dim3(BLOCK), 0, st_, in, H, W, C, w, bias, out);
   else if (wide) hipLaunchKernelGGL((k_dwconv<false, 4>), g, dim3(BLOCK), 0, st_, in, H, W, C, w, bias, out);
   else hipLaunchKernelGGL((k_dwconv<false, 1>), g, dim3(BLOCK), 0, st_, in, H, W, C, w, bias, out);
-  PW_CHECK_LAUNCH("k_dwconv");
+  SIDE_CHECK_LAUNCH("k_dwconv");
   return 0;
 }
 
@@ -585,7 +566,7 @@ int PW_FN(inflate)(const float *tokens, int64_t n, int32_t C, const float *scale
   else
     hipLaunchKernelGGL(k_inflate<1>, dim3(blocks_for(n * C)), dim3(BLOCK), 0, st_, tokens, n, C, scale, grid, cell, ncell, out,
                        d_status);
-  PW_CHECK_LAUNCH("k_inflate");
+  SIDE_CHECK_LAUNCH("k_inflate");
   return 0;
 }
 
@@ -599,7 +580,7 @@ int PW_FN(neigh_rows)(const float *feat, int64_t n, int32_t F, const int32_t *kn
   if (np == 0) return 0;
   hipLaunchKernelGGL(k_neigh, dim3(blocks_for(np * k * C)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), feat, n, F, knn,
                      k, p0, np * k, A, b, C, rows, d_status);
-  PW_CHECK_LAUNCH("k_neigh");
+  SIDE_CHECK_LAUNCH("k_neigh");
   return 0;
 }
 
@@ -610,7 +591,7 @@ int PW_FN(group_max)(const float *rows, int64_t np, int32_t k, int32_t C, float 
   if (np == 0) return 0;
   hipLaunchKernelGGL(k_group_max, dim3(blocks_for(np * C)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), rows, np, k, C,
                      out, ld_out);
-  PW_CHECK_LAUNCH("k_group_max");
+  SIDE_CHECK_LAUNCH("k_group_max");
   return 0;
 }
 

@@ -5,12 +5,11 @@ kernels.  Every method takes device tensors, enqueues on the caller's current st
 from __future__ import annotations
 
 import ctypes as C
-import threading
 from typing import Optional, Sequence, Tuple
 
 import torch
 
-from ..me.backend import HIP_LIB_PATH
+from .._clib import FamilyLib, shared
 
 PF_ABI_VERSION = 1       # include/pasco_frame.h PF_ABI_VERSION this binding was written against
 MAX_SEGMENTS = 4
@@ -29,16 +28,18 @@ class PointsArgs(C.Structure):
 
 
 _vp, _i64, _i32 = C.c_void_p, C.c_int64, C.c_int32
+# name -> argtypes (everything returns int unless listed in _RESTYPES)
 _SIGNATURES = {
-    "abi_version": ([], C.c_int),
-    "last_error": ([], C.c_char_p),
-    "points_channels": ([C.POINTER(PointsArgs)], _i32),
-    "points_workspace_bytes": ([_i64], _i64),
-    "points": ([_vp, _i64, C.POINTER(PointsArgs), _vp, _vp, _vp, _vp, _vp, _i64, _vp], C.c_int),
-    "transform_coords": ([_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp], C.c_int),
-    "bounds_workspace_bytes": ([_i32], _i64),
-    "label_bounds": ([_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp], C.c_int),
+    "abi_version": [],
+    "last_error": [],
+    "points_channels": [C.POINTER(PointsArgs)],
+    "points_workspace_bytes": [_i64],
+    "points": [_vp, _i64, C.POINTER(PointsArgs), _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "transform_coords": [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp],
+    "bounds_workspace_bytes": [_i32],
+    "label_bounds": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp],
 }
+_RESTYPES = {"last_error": C.c_char_p, "points_workspace_bytes": _i64, "bounds_workspace_bytes": _i64}
 
 
 def _seg(t: torch.Tensor, width: int, row_stride: int, col_stride: int) -> Segment:
@@ -58,23 +59,9 @@ def _mats(Ts: Sequence[torch.Tensor]):
     return (C.c_float * flat.numel())(*flat.tolist())
 
 
-class FrameLib:
-    def __init__(self, path: str = HIP_LIB_PATH):
-        self.lib = C.CDLL(path)
-        for name, (args, res) in _SIGNATURES.items():
-            fn = getattr(self.lib, "pf_" + name)
-            fn.argtypes, fn.restype = args, res
-        v = self.lib.pf_abi_version()
-        if v != PF_ABI_VERSION:
-            raise RuntimeError(f"{path}: pf ABI {v}, this binding needs {PF_ABI_VERSION}; rebuild (pasco_amd/build.py)")
-
-    def _ok(self, rc: int, what: str):
-        if rc != 0:
-            raise RuntimeError(f"pf_{what}: {self.lib.pf_last_error().decode()}")
-
-    @staticmethod
-    def _stream(t: torch.Tensor):
-        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+class FrameLib(FamilyLib):
+    def __init__(self, path: Optional[str] = None):
+        super().__init__("pf_", PF_ABI_VERSION, _SIGNATURES, _RESTYPES, path)
 
     @staticmethod
     def points_args(lo, hi, lo_fp64, hi_fp64, origin, voxel: float, centre_fp64: bool,
@@ -143,17 +130,9 @@ class FrameLib:
         return out
 
 
-_LIB = None
-_LOCK = threading.Lock()
-
-
 def frame_lib() -> FrameLib:
     """The process-wide binding of libpascohip.so's frame kernels (a missing library is an error)."""
-    global _LIB
-    with _LOCK:
-        if _LIB is None:
-            _LIB = FrameLib()
-        return _LIB
+    return shared(FrameLib)
 
 
 def box_upper_bound(grid: Tuple[int, int, int], Ts: Sequence[torch.Tensor], margin: int = 2) -> torch.Tensor:

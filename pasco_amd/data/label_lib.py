@@ -5,12 +5,11 @@ Every method takes device tensors and enqueues on the caller's current stream; n
 from __future__ import annotations
 
 import ctypes as C
-import threading
 from typing import Optional, Sequence
 
 import torch
 
-from ..me.backend import HIP_LIB_PATH
+from .._clib import FamilyLib, shared
 
 PL_ABI_VERSION = 1       # include/pasco_label.h PL_ABI_VERSION this binding was written against
 MAX_THINGS = 32
@@ -19,32 +18,20 @@ REC_INSTANCES, REC_DROPPED, REC_UNKNOWN, REC_STATUS = 0, 1, 2, 3
 STATUS_RAW_RANGE, STATUS_LOOP_CAP = 1, 2
 
 _vp, _i64, _i32 = C.c_void_p, C.c_int64, C.c_int32
+# name -> argtypes (everything returns int unless listed in _RESTYPES)
 _SIGNATURES = {
-    "abi_version": ([], C.c_int),
-    "last_error": ([], C.c_char_p),
-    "semantic_grid": ([_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp], C.c_int),
-    "instances_workspace_bytes": ([_i32, _i32, _i32, _i32], _i64),
-    "instances": ([_vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp], C.c_int),
+    "abi_version": [],
+    "last_error": [],
+    "semantic_grid": [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp],
+    "instances_workspace_bytes": [_i32, _i32, _i32, _i32],
+    "instances": [_vp, _i32, _i32, _i32, C.POINTER(_i32), _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
 }
+_RESTYPES = {"last_error": C.c_char_p, "instances_workspace_bytes": _i64}
 
 
-class LabelLib:
-    def __init__(self, path: str = HIP_LIB_PATH):
-        self.lib = C.CDLL(path)
-        for name, (args, res) in _SIGNATURES.items():
-            fn = getattr(self.lib, "pl_" + name)
-            fn.argtypes, fn.restype = args, res
-        v = self.lib.pl_abi_version()
-        if v != PL_ABI_VERSION:
-            raise RuntimeError(f"{path}: pl ABI {v}, this binding needs {PL_ABI_VERSION}; rebuild (pasco_amd/build.py)")
-
-    def _ok(self, rc: int, what: str):
-        if rc != 0:
-            raise RuntimeError(f"pl_{what}: {self.lib.pl_last_error().decode()}")
-
-    @staticmethod
-    def _stream(t: torch.Tensor):
-        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+class LabelLib(FamilyLib):
+    def __init__(self, path: Optional[str] = None):
+        super().__init__("pl_", PL_ABI_VERSION, _SIGNATURES, _RESTYPES, path)
 
     def semantic_grid(self, raw: torch.Tensor, invalid: torch.Tensor, lut: torch.Tensor,
                       status: Optional[torch.Tensor] = None):
@@ -112,14 +99,6 @@ class LabelLib:
                                        ws.numel(), self._stream(sem)), "instances")
 
 
-_LIB = None
-_LOCK = threading.Lock()
-
-
 def label_lib() -> LabelLib:
     """The process-wide binding of libpascohip.so's label kernels (a missing library is an error)."""
-    global _LIB
-    with _LOCK:
-        if _LIB is None:
-            _LIB = LabelLib()
-        return _LIB
+    return shared(LabelLib)

@@ -4,11 +4,11 @@ Kept apart from `me.backend` on purpose: the CPU oracle binds `me.backend._SIGNA
 from __future__ import annotations
 
 import ctypes as C
-import threading
+from typing import Optional
 
 import torch
 
-from ..me.backend import HIP_LIB_PATH
+from .._clib import FamilyLib, shared
 
 PE_ABI_VERSION = 1       # include/pasco_eval.h PE_ABI_VERSION this binding was written against
 BINS = 16
@@ -27,39 +27,27 @@ ECE_COUNTS = 2 * BINS
 ECE_SUMS = BINS
 
 _vp, _i64, _i32 = C.c_void_p, C.c_int64, C.c_int32
+# name -> argtypes (everything returns int unless listed in _RESTYPES)
 _SIGNATURES = {
-    "abi_version": ([], C.c_int),
-    "last_error": ([], C.c_char_p),
-    "ssc_workspace_bytes": ([_i64, _i32], _i64),
-    "ece_workspace_bytes": ([_i64], _i64),
-    "ssc": ([_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp], C.c_int),
-    "panop_pairs": ([_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp], C.c_int),
-    "match": ([_vp, _vp, _vp, _i32, _i32, _vp, _vp], C.c_int),
-    "mask_ece": ([_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp], C.c_int),
+    "abi_version": [],
+    "last_error": [],
+    "ssc_workspace_bytes": [_i64, _i32],
+    "ece_workspace_bytes": [_i64],
+    "ssc": [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp],
+    "panop_pairs": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
+    "match": [_vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "mask_ece": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp],
 }
+_RESTYPES = {"last_error": C.c_char_p, "ssc_workspace_bytes": _i64, "ece_workspace_bytes": _i64}
 
 
-class EvalLib:
+class EvalLib(FamilyLib):
     """The evaluation kernels on the caller's current stream.  Every method takes device tensors and returns nothing: the
     results land in the caller's output tensors (one buffer per scene, read back once)."""
 
-    def __init__(self, path: str = HIP_LIB_PATH):
-        self.lib = C.CDLL(path)
-        for name, (args, res) in _SIGNATURES.items():
-            fn = getattr(self.lib, "pe_" + name)
-            fn.argtypes, fn.restype = args, res
-        v = self.lib.pe_abi_version()
-        if v != PE_ABI_VERSION:
-            raise RuntimeError(f"{path}: pe ABI {v}, this binding needs {PE_ABI_VERSION}; rebuild (pasco_amd/build.py)")
+    def __init__(self, path: Optional[str] = None):
+        super().__init__("pe_", PE_ABI_VERSION, _SIGNATURES, _RESTYPES, path)
         self._edges = (C.c_float * BINS)(*torch.linspace(0, 1, BINS).tolist())
-
-    def _ok(self, rc: int, what: str):
-        if rc != 0:
-            raise RuntimeError(f"pe_{what}: {self.lib.pe_last_error().decode()}")
-
-    @staticmethod
-    def _stream(t: torch.Tensor):
-        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
     def ssc_workspace_bytes(self, n_sites: int, c: int) -> int:
         return int(self.lib.pe_ssc_workspace_bytes(n_sites, c))
@@ -91,14 +79,6 @@ class EvalLib:
                                       ws.numel() * ws.element_size(), counts_ptr, sums_ptr, self._stream(conf)), "mask_ece")
 
 
-_LIB = None
-_LOCK = threading.Lock()
-
-
 def eval_lib() -> EvalLib:
     """The process-wide binding of libpascohip.so's evaluation kernels (a missing library is an error)."""
-    global _LIB
-    with _LOCK:
-        if _LIB is None:
-            _LIB = EvalLib()
-        return _LIB
+    return shared(EvalLib)

@@ -16,6 +16,8 @@ from typing import Dict, Optional
 
 import torch
 
+from .._clib import _raw_stream, bind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(os.path.dirname(_HERE), "csrc", "libpascohip.so")
 
@@ -132,7 +134,6 @@ _SIGNATURES = {
     "panop_write": [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {"last_error": C.c_char_p, "workspace_bytes": _i64, "attn_workspace_bytes": _i64}
-_OPTIONAL = {}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 
@@ -160,7 +161,6 @@ class CBackend:
         self.device_type = device_type
         self._serves_cuda = device_type == "cuda"
         self.lib = C.CDLL(path)
-        self.fn: Dict[str, object] = {}
         # handshake BEFORE anything else is bound: version, then the size of the one struct that crosses the boundary
         ver = getattr(self.lib, prefix + "abi_version", None)
         v = int(ver()) if ver is not None else -1
@@ -171,17 +171,7 @@ class CBackend:
         if dsz is None or int(dsz()) != C.sizeof(ConvDesc):
             raise RuntimeError(f"{path}: sizeof(ph_conv_desc) = {None if dsz is None else int(dsz())}, the binding's mirror has "
                                f"{C.sizeof(ConvDesc)} bytes - rebuild the library against include/pasco_hip.h")
-        for name, argtypes in _SIGNATURES.items():
-            f = getattr(self.lib, prefix + name)
-            f.argtypes = argtypes
-            f.restype = _RESTYPES.get(name, C.c_int)
-            self.fn[name] = f
-        for name, argtypes in _OPTIONAL.items():
-            f = getattr(self.lib, prefix + name, None)
-            if f is not None:
-                f.argtypes = argtypes
-                f.restype = C.c_int
-                self.fn[name] = f
+        self.fn = bind(self.lib, prefix, _SIGNATURES, _RESTYPES)
         self._ws: Dict[torch.device, torch.Tensor] = {}
         self._status_ptrs: Dict[tuple, int] = {}         # (device type, index, stream handle) -> address of the status pair
         self._tls = threading.local()
@@ -1276,12 +1266,6 @@ class CBackend:
         return {"panoptic": per_i[1, :n], "semantic": per_i[2, :n], "ins_unc": per_f[2, :n], "vox_conf": per_f[3, :n],
                 "vox_unc": per_f[4, :n], "winner": per_i[0, :n], "own": own[:n], "qtab": qtab, "nk": nk, "seg": seg,
                 "areas": areas, "tabs": tabs}
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-if _raw_stream is None:      # older torch: the public (slower) route
-    def _raw_stream(idx: int) -> int:
-        return torch.cuda.current_stream(idx).cuda_stream
 
 
 # ---- registry -----------------------------------------------------------------------------------

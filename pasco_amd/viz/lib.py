@@ -5,53 +5,34 @@ Every method takes device tensors and enqueues on the caller's current stream; n
 from __future__ import annotations
 
 import ctypes as C
-import threading
 from typing import Optional, Sequence
 
 import torch
 
-from ..me.backend import HIP_LIB_PATH
+from .._clib import FamilyLib, dev_ptr as _dev, shared
 from .host import OPS, VIEWS
 
 PV_ABI_VERSION = 1       # include/pasco_view.h PV_ABI_VERSION this binding was written against
 
 _vp, _i64, _i32, _u32, _f32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_float
+# name -> argtypes (everything returns int unless listed in _RESTYPES)
 _SIGNATURES = {
-    "abi_version": ([], C.c_int),
-    "last_error": ([], C.c_char_p),
-    "majority_pool": ([_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp], C.c_int),
-    "window_filter": ([_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp], C.c_int),
-    "compose": ([_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp], C.c_int),
-    "brick_words": ([_i32, _i32, _i32], _i64),
-    "bricks": ([_vp, _i32, _i32, _i32, _vp, _vp], C.c_int),
-    "render": ([_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _u32, _i32, _vp, _vp, _vp, _vp, _vp],
-               C.c_int),
-    "downsample": ([_vp, _i32, _i32, _i32, _vp, _vp], C.c_int),
+    "abi_version": [],
+    "last_error": [],
+    "majority_pool": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "window_filter": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "compose": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp],
+    "brick_words": [_i32, _i32, _i32],
+    "bricks": [_vp, _i32, _i32, _i32, _vp, _vp],
+    "render": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _u32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "downsample": [_vp, _i32, _i32, _i32, _vp, _vp],
 }
+_RESTYPES = {"last_error": C.c_char_p, "brick_words": _i64}
 
 
-def _dev(t: torch.Tensor, dtype, what: str):
-    assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), f"{what}: a contiguous {dtype} device tensor"
-    return t.data_ptr()
-
-
-class ViewLib:
-    def __init__(self, path: str = HIP_LIB_PATH):
-        self.lib = C.CDLL(path)
-        for name, (args, res) in _SIGNATURES.items():
-            fn = getattr(self.lib, "pv_" + name)
-            fn.argtypes, fn.restype = args, res
-        v = self.lib.pv_abi_version()
-        if v != PV_ABI_VERSION:
-            raise RuntimeError(f"{path}: pv ABI {v}, this binding needs {PV_ABI_VERSION}; rebuild (pasco_amd/build.py)")
-
-    def _ok(self, rc: int, what: str):
-        if rc != 0:
-            raise RuntimeError(f"pv_{what}: {self.lib.pv_last_error().decode()}")
-
-    @staticmethod
-    def _stream(t: torch.Tensor):
-        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+class ViewLib(FamilyLib):
+    def __init__(self, path: Optional[str] = None):
+        super().__init__("pv_", PV_ABI_VERSION, _SIGNATURES, _RESTYPES, path)
 
     def majority_pool(self, grid: torch.Tensor, k: int, out: Optional[torch.Tensor] = None,
                       status: Optional[torch.Tensor] = None):
@@ -147,14 +128,6 @@ class ViewLib:
         return out
 
 
-_LIB = None
-_LOCK = threading.Lock()
-
-
 def view_lib() -> ViewLib:
     """The process-wide binding of libpascohip.so's view kernels (a missing library is an error)."""
-    global _LIB
-    with _LOCK:
-        if _LIB is None:
-            _LIB = ViewLib()
-        return _LIB
+    return shared(ViewLib)

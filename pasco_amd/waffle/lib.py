@@ -6,38 +6,34 @@ plumbing is the stable sort in `cells_build` (the kernel checks the permutation 
 from __future__ import annotations
 
 import ctypes as C
-import threading
 from typing import Optional
 
 import torch
 
-from ..me.backend import HIP_LIB_PATH
+from .._clib import FamilyLib, dev_ptr as _dev, shared
 from .host import SearchGrid
 
 PW_ABI_VERSION = 1       # include/pasco_waffle.h PW_ABI_VERSION this binding was written against
 
 _vp, _i64, _i32, _f32, _f64 = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_double
 _GRID = [_f64, _f64, _f64, _f64, _i32, _i32, _i32]
+# name -> argtypes (everything returns int unless listed in _RESTYPES)
 _SIGNATURES = {
-    "abi_version": ([], C.c_int),
-    "last_error": ([], C.c_char_p),
-    "voxel_keys": ([_vp, _i32, _i64, _vp, _f32, _vp, _vp, _vp], C.c_int),
-    "cell_index": ([_vp, _i32, _i64, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _vp], C.c_int),
-    "grid_cells": ([_vp, _i32, _i64, *_GRID, _vp, _vp, _vp], C.c_int),
-    "cells_build": ([_vp, _vp, _i64, _i32, _vp, _vp, _vp], C.c_int),
-    "knn": ([_vp, _i32, _i64, _vp, _vp, *_GRID, _i32, _vp, _vp], C.c_int),
-    "nearest": ([_vp, _i32, _i64, _vp, _vp, *_GRID, _vp, _i32, _i64, _vp, _vp], C.c_int),
-    "flatten": ([_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp], C.c_int),
-    "dwconv3x3": ([_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp], C.c_int),
-    "inflate": ([_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp], C.c_int),
-    "neigh_rows": ([_vp, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp], C.c_int),
-    "group_max": ([_vp, _i64, _i32, _i32, _vp, _i32, _vp], C.c_int),
+    "abi_version": [],
+    "last_error": [],
+    "voxel_keys": [_vp, _i32, _i64, _vp, _f32, _vp, _vp, _vp],
+    "cell_index": [_vp, _i32, _i64, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _vp],
+    "grid_cells": [_vp, _i32, _i64, *_GRID, _vp, _vp, _vp],
+    "cells_build": [_vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "knn": [_vp, _i32, _i64, _vp, _vp, *_GRID, _i32, _vp, _vp],
+    "nearest": [_vp, _i32, _i64, _vp, _vp, *_GRID, _vp, _i32, _i64, _vp, _vp],
+    "flatten": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "dwconv3x3": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
+    "inflate": [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "neigh_rows": [_vp, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
+    "group_max": [_vp, _i64, _i32, _i32, _vp, _i32, _vp],
 }
-
-
-def _dev(t: torch.Tensor, dtype, what: str):
-    assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), f"{what}: a contiguous {dtype} device tensor"
-    return t.data_ptr()
+_RESTYPES = {"last_error": C.c_char_p}
 
 
 def _rows(t: torch.Tensor, what: str):
@@ -46,23 +42,9 @@ def _rows(t: torch.Tensor, what: str):
     return t.data_ptr(), int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
 
 
-class WaffleLib:
-    def __init__(self, path: str = HIP_LIB_PATH):
-        self.lib = C.CDLL(path)
-        for name, (args, res) in _SIGNATURES.items():
-            fn = getattr(self.lib, "pw_" + name)
-            fn.argtypes, fn.restype = args, res
-        v = self.lib.pw_abi_version()
-        if v != PW_ABI_VERSION:
-            raise RuntimeError(f"{path}: pw ABI {v}, this binding needs {PW_ABI_VERSION}; rebuild (pasco_amd/build.py)")
-
-    def _ok(self, rc: int, what: str):
-        if rc != 0:
-            raise RuntimeError(f"pw_{what}: {self.lib.pw_last_error().decode()}")
-
-    @staticmethod
-    def _stream(t: torch.Tensor):
-        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+class WaffleLib(FamilyLib):
+    def __init__(self, path: Optional[str] = None):
+        super().__init__("pw_", PW_ABI_VERSION, _SIGNATURES, _RESTYPES, path)
 
     @staticmethod
     def new_status(device) -> torch.Tensor:
@@ -198,14 +180,6 @@ class WaffleLib:
         return out
 
 
-_LIB = None
-_LOCK = threading.Lock()
-
-
 def waffle_lib() -> WaffleLib:
     """The process-wide binding of libpascohip.so's waffle kernels (a missing library is an error)."""
-    global _LIB
-    with _LOCK:
-        if _LIB is None:
-            _LIB = WaffleLib()
-        return _LIB
+    return shared(WaffleLib)
