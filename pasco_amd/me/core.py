@@ -349,6 +349,18 @@ class CoordinateManager:
             cache[key] = hit
         return hit[1]
 
+    def kernel_map_inverse(self, nbr: torch.Tensor, n_in: int) -> torch.Tensor:
+        """inv int32 [kvol, n_in] of a neighbour table of this manager: inv[k][nbr[k][o]] = o, -1 elsewhere - the table the
+        input gradient of a convolution gathers through (include/pasco_grad.h pg_nbr_invert), built once per map."""
+        cache = self.__dict__.setdefault("_inv_cache", {})
+        key = (nbr.data_ptr(), int(n_in))
+        hit = cache.get(key)
+        if hit is None or hit[0] is not nbr:
+            from ..grad import nbr_invert
+            hit = (nbr, nbr_invert(nbr, int(n_in)))
+            cache[key] = hit
+        return hit[1]
+
     def kernel_rowlist(self, nbr: torch.Tensor):
         """Row lists of a one-pair-per-row neighbour table of this manager (backend.rowlist_build), built once per map."""
         cache = self.__dict__.setdefault("_rl_cache", {})
@@ -508,11 +520,21 @@ class SparseTensor:
         # the union lists the lhs rows first, in their order (a map's coordinates are unique, so every lhs row is its own first
         # occurrence): the lhs features are a plain copy into the leading rows, only the rhs rows are scattered
         na = self._F.shape[0]
-        out = torch.empty((n_out, self._F.shape[1]), dtype=self._F.dtype, device=self._F.device)
-        out[:na].copy_(self.F)
-        if n_out > na:
-            out[na:].zero_()
-        be.scatter_add_rows(other.F.contiguous(), b2o.contiguous(), out)
+
+        def launch(fa, fb):
+            out = torch.empty((n_out, fa.shape[1]), dtype=fa.dtype, device=fa.device)
+            out[:na].copy_(fa)
+            if n_out > na:
+                out[na:].zero_()
+            be.scatter_add_rows(fb.contiguous(), b2o.contiguous(), out)
+            return out
+
+        fa, fb = self.F, other.F
+        if torch.is_grad_enabled() and (fa.requires_grad or fb.requires_grad):
+            from .autograd import UnionAddFunction
+            out = UnionAddFunction.apply(fa, fb, b2o, launch, be)
+        else:
+            out = launch(fa, fb)
         return SparseTensor(out, coordinate_map_key=key, coordinate_manager=self._manager)
 
     def __add__(self, other):

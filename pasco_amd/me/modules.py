@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import backend as B
+from .autograd import ConvFunction, GatherRowsFunction, wants_grad
 from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple, tensor_version
 
 
@@ -105,7 +106,20 @@ class _ConvBase(MinkowskiModuleBase):
         the exact fp32 MFMA runs at 1 / 16 of the f16 rate and was ~85 % of the unfused route's time).
         `PASCO_ME_CONV=exact` (or `set_me_conv("exact")`): the exact kernel only.
         `prologue` = (scale, shift, act, slope) of a deferred BatchNorm / activation in front (SparseTensor.deferred): applied
-        to the gathered rows by the launch itself instead of by separate passes over the tensor."""
+        to the gathered rows by the launch itself instead of by separate passes over the tensor.
+        With autograd enabled and features, kernel or bias requiring grad the same launches run inside
+        `autograd.ConvFunction`, which gives the result its `grad_fn` (backward: include/pasco_grad.h)."""
+        if torch.is_grad_enabled():
+            exact = self.kernel.requires_grad and self.training
+            if prologue is None and wants_grad(feats, self.kernel, self.bias):
+                return ConvFunction.apply(feats, self.kernel, self.bias,
+                                          lambda f: self._launch(be, f, nbr, n_out, mgr, None, exact), be, nbr, n_out, mgr)
+            return self._launch(be, feats, nbr, n_out, mgr, prologue, exact)
+        return self._launch(be, feats, nbr, n_out, mgr, prologue, False)
+
+    def _launch(self, be, feats: torch.Tensor, nbr, n_out: int, mgr, prologue, exact: bool) -> torch.Tensor:
+        """The launches of `conv_rows` on detached parameters; `exact` = a training-mode kernel that requires grad, seen with
+        autograd enabled: the exact fp32 route only."""
         feats = feats.contiguous()
         kernel = self.kernel.detach().contiguous()
         bias = self.bias.detach().reshape(-1).contiguous() if self.bias is not None else None
@@ -113,8 +127,7 @@ class _ConvBase(MinkowskiModuleBase):
         if prologue is not None:
             ps, pb, pact, pslope = prologue
             pro = dict(pro_scale=ps, pro_shift=pb, pro_act=pact, slope=pslope)
-        if n_out == 0 or _ME_CONV != "guarded" or not be.split_supported(self.in_channels, self.out_channels) or \
-                torch.is_grad_enabled() and self.kernel.requires_grad and self.training:
+        if n_out == 0 or _ME_CONV != "guarded" or not be.split_supported(self.in_channels, self.out_channels) or exact:
             return be.conv_fwd(feats, kernel, nbr, n_out, bias=bias, **pro)
         w = self.kernel
         v = tensor_version(w)         # None: a parameter made under torch.inference_mode() - no version counter, split every call
@@ -311,7 +324,10 @@ class MinkowskiPruning(MinkowskiModuleBase):
             mask = mask != 0
         mgr = x.coordinate_manager
         out_key, keep = mgr.prune(x.coordinate_map_key, mask.to(x.device))
-        feats = mgr.backend().gather_rows(x.F.contiguous(), keep)
+        if wants_grad(x.F):
+            feats = GatherRowsFunction.apply(x.F, keep, mgr.backend())
+        else:
+            feats = mgr.backend().gather_rows(x.F.contiguous(), keep)
         return SparseTensor(feats, coordinate_map_key=out_key, coordinate_manager=mgr)
 
 
