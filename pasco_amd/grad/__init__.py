@@ -1,7 +1,8 @@
 """Training operators of the sparse convolution family (include/pasco_grad.h): the inverse of a neighbour table, the weight
-gradient and the bias gradient.  `host` restates the three in torch (CPU tensors, the tensor's dtype), `lib` binds the `pg_*`
-entry points; `nbr_invert`, `conv_wgrad` and `colsum` here serve a tensor from the one its device calls for.  The autograd
-functions that use them are `pasco_amd.me.autograd`."""
+gradient and the bias gradient; and of the dense <-> rows operators and local max pooling (include/pasco_rowgrad.h).  `host`
+restates them in torch (CPU tensors, the tensor's dtype), `lib` binds the `pg_*` entry points and `rowlib` the `pr_*` ones; the
+functions here serve a tensor from the one its device calls for.  The autograd functions that use them are
+`pasco_amd.me.autograd`."""
 from __future__ import annotations
 
 import torch
@@ -28,3 +29,31 @@ def colsum(dy: torch.Tensor) -> torch.Tensor:
         from .lib import grad_lib
         return grad_lib().colsum(dy)
     return host.colsum(dy)
+
+
+def dense_rows(dense: torch.Tensor, coords: torch.Tensor, min3, ts: int) -> torch.Tensor:
+    if dense.is_cuda:
+        from .rowlib import rowgrad_lib
+        return rowgrad_lib().dense_rows(dense, coords, min3, ts)
+    return host.dense_rows(dense, coords, min3, ts)
+
+
+def rows_dense(rows: torch.Tensor, site_coords: torch.Tensor, shape5) -> torch.Tensor:
+    if rows.is_cuda:
+        from .rowlib import rowgrad_lib
+        return rowgrad_lib().rows_dense(rows, site_coords, shape5)
+    return host.rows_dense(rows, site_coords, shape5)
+
+
+def maxpool_arg(x: torch.Tensor, nbr: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    if x.is_cuda:
+        from .rowlib import rowgrad_lib
+        return rowgrad_lib().maxpool_arg(x, nbr, out)
+    return host.maxpool_arg(x, nbr, out)
+
+
+def maxpool_bwd(dy: torch.Tensor, arg: torch.Tensor, inv: torch.Tensor, n_in: int) -> torch.Tensor:
+    if dy.is_cuda:
+        from .rowlib import rowgrad_lib
+        return rowgrad_lib().maxpool_bwd(dy, arg, inv, n_in)
+    return host.maxpool_bwd(dy, arg, inv, n_in)

@@ -1,4 +1,5 @@
-"""Torch restatement of include/pasco_grad.h for CPU tensors: index operations and matrix products in the tensor's dtype.  The
+"""Torch restatement of include/pasco_grad.h and include/pasco_rowgrad.h for CPU tensors: index operations and matrix products in
+the tensor's dtype.  The
 CPU tests run on it and `pasco_amd.me.autograd` uses it where the features are not on a GPU.  Same results as the kernels up to
 the order of the fp32 sums."""
 from __future__ import annotations
@@ -36,3 +37,69 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, nbr: torch.Tensor) -> torch.Te
 def colsum(dy: torch.Tensor) -> torch.Tensor:
     """dy [n, c] -> [c]."""
     return dy.sum(dim=0)
+
+
+# ---- include/pasco_rowgrad.h ------------------------------------------------------------------------------------------------
+def _dense_sites(coords: torch.Tensor, min3, ts: int, dims4, wrap: bool):
+    """coords int [n, 4] -> (ok bool [n], b, x, y, z int64 [n]): the site of every row by ph_to_dense's rule (`wrap`: an index in
+    [-dim, 0) wraps) or ph_dense_gather's (min 0, ts 1, no wrap); ok = the forward does not skip the row."""
+    c = coords.long()
+    dims = [int(v) for v in dims4]
+    ok = (c[:, 0] >= 0) & (c[:, 0] < dims[0])
+    idx = [c[:, 0]]
+    for a in range(3):
+        v = torch.div(c[:, 1 + a] - int(min3[a]), int(ts), rounding_mode="floor")
+        if wrap:
+            v = torch.where(v < 0, v + dims[1 + a], v)
+        ok = ok & (v >= 0) & (v < dims[1 + a])
+        idx.append(v)
+    return (ok, *idx)
+
+
+def dense_rows(dense: torch.Tensor, coords: torch.Tensor, min3, ts: int) -> torch.Tensor:
+    """dense [B, C, X, Y, Z], coords int32 [n, 4] -> rows [n, C] = dense[b_i, :, site(i)], zero rows where the forward skips."""
+    B, C, X, Y, Z = dense.shape
+    ok, b, x, y, z = _dense_sites(coords, min3, ts, (B, X, Y, Z), True)
+    rows = torch.zeros((coords.shape[0], C), dtype=dense.dtype, device=dense.device)
+    if bool(ok.any()):
+        rows[ok] = dense[b[ok], :, x[ok], y[ok], z[ok]]
+    return rows
+
+
+def rows_dense(rows: torch.Tensor, site_coords: torch.Tensor, shape5) -> torch.Tensor:
+    """rows [n, C], site_coords int32 [n, 4] (distinct in-range sites) -> dense of `shape5`, zero except rows[i] at row i's site."""
+    B, C, X, Y, Z = (int(v) for v in shape5)
+    ok, b, x, y, z = _dense_sites(site_coords, (0, 0, 0), 1, (B, X, Y, Z), False)
+    dense = torch.zeros((B, C, X, Y, Z), dtype=rows.dtype, device=rows.device)
+    if bool(ok.any()):
+        dense[b[ok], :, x[ok], y[ok], z[ok]] = rows[ok]
+    return dense
+
+
+def maxpool_arg(x: torch.Tensor, nbr: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """x [n_in, C], nbr int32 [K, n_out], out [n_out, C] -> arg int32 [n_out, C]: the input row of the first offset (ascending k)
+    whose value == out, -1 where there is none."""
+    K, n_out = nbr.shape
+    n_in = x.shape[0]
+    arg = torch.full(out.shape, -1, dtype=torch.int32, device=x.device)
+    for k in range(K - 1, -1, -1):                # descending, so the smallest k is written last
+        r = nbr[k].long()
+        have = (r >= 0) & (r < n_in)
+        hit = have[:, None] & (x[r.clamp(0, max(n_in - 1, 0))] == out) if n_in else torch.zeros_like(out, dtype=torch.bool)
+        arg = torch.where(hit, nbr[k][:, None].expand_as(arg), arg)
+    return arg
+
+
+def maxpool_bwd(dy: torch.Tensor, arg: torch.Tensor, inv: torch.Tensor, n_in: int) -> torch.Tensor:
+    """dy [n_out, C], arg int32 [n_out, C], inv int32 [K, n_in] -> dx [n_in, C]: terms added in ascending k."""
+    n_out, C = dy.shape
+    dx = torch.zeros((n_in, C), dtype=dy.dtype, device=dy.device)
+    if n_in == 0 or n_out == 0:
+        return dx
+    rows = torch.arange(n_in, device=dy.device, dtype=arg.dtype)[:, None]
+    for k in range(inv.shape[0]):
+        o = inv[k].long()
+        have = (o >= 0) & (o < n_out)
+        oc = o.clamp(0, n_out - 1)
+        dx = dx + torch.where(have[:, None] & (arg[oc] == rows), dy[oc], torch.zeros_like(dx))
+    return dx

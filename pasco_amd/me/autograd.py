@@ -1,12 +1,15 @@
 """Autograd of the sparse convolution family: `MinkowskiConvolution` / `...Transpose` / `...GenerativeConvolutionTranspose`,
-`MinkowskiPruning` and the two-map `SparseTensor.__add__`.
+`MinkowskiPruning` and the two-map `SparseTensor.__add__`; and of the operators between them: `SparseTensor.dense()`,
+`to_sparse()`, the duplicate-dropping `SparseTensor(features, coordinates)` and `MinkowskiMaxPooling`.
 
 Each function's `forward` performs the very launches the module performs without autograd (the caller passes its own launch
 helper), so the forward values are the same bits in every mode; only the `grad_fn` is new.  The backward launches are
-include/pasco_grad.h on the device and `pasco_amd.grad.host` for CPU tensors.  Once differentiable: no double backward.
+include/pasco_grad.h and include/pasco_rowgrad.h on the device and `pasco_amd.grad.host` for CPU tensors.  Once differentiable:
+no double backward.
 
 Used only when autograd is enabled and an input requires grad (`modules._ConvBase.conv_rows`, `MinkowskiPruning.forward`,
-`SparseTensor._binary`); the inference paths never come here."""
+`MinkowskiMaxPooling.forward`, `SparseTensor.__init__` / `._binary` / `.dense`, `core.to_sparse`); the inference paths never come
+here."""
 from __future__ import annotations
 
 import torch
@@ -99,3 +102,64 @@ class UnionAddFunction(torch.autograd.Function):
         d_a = g[:ctx.na] if ctx.needs_input_grad[0] else None
         d_b = ctx.be.gather_rows(g, b2o.contiguous()) if ctx.needs_input_grad[1] else None
         return d_a, d_b, None, None, None
+
+
+class DenseFunction(torch.autograd.Function):
+    """`SparseTensor.dense()`: dense[b_i, :, site(i)] = feats[i] (`be.to_dense`).  The backward reads every row's site back:
+    d_feats[i] = g[b_i, :, site(i)], a zero row where the forward skipped the row (outside the grid after the wrap of an index in
+    [-dim, 0), or a batch index outside).  Several rows on one site (only a wrap produces them) EACH receive that site's
+    gradient although the forward kept only one of them: it is what torch's autograd gives for `index_put_`, and which row
+    stayed is not recorded anywhere."""
+
+    @staticmethod
+    def forward(ctx, feats, coords, min3, step, dims, be):
+        ctx.save_for_backward(coords)
+        ctx.min3, ctx.step = tuple(min3), int(step)
+        return be.to_dense(feats.contiguous(), coords, min3, step, dims)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (coords,) = ctx.saved_tensors
+        return G.dense_rows(g.contiguous(), coords, ctx.min3, ctx.step), None, None, None, None, None
+
+
+class ToSparseFunction(torch.autograd.Function):
+    """`to_sparse()`: -> (coords, feats) of `be.to_sparse` (the site scan, then `be.dense_gather`).  The coordinates are decided
+    from the values and carry no gradient; the backward stores g[i] at row i's site of a zero tensor of the dense's shape (the
+    sites are distinct and in range by construction)."""
+
+    @staticmethod
+    def forward(ctx, x, be):
+        coords, feats = be.to_sparse(x)
+        ctx.mark_non_differentiable(coords)
+        ctx.save_for_backward(coords)
+        ctx.shape = tuple(x.shape)
+        return coords, feats
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _g_coords, g):
+        (coords,) = ctx.saved_tensors
+        return G.rows_dense(g.contiguous(), coords, ctx.shape), None
+
+
+class MaxPoolFunction(torch.autograd.Function):
+    """`MinkowskiMaxPooling`: out = `be.maxpool_fwd(x, nbr)`.  The forward also records arg[o][c] = the input row of the first
+    offset whose value == out[o][c] (-1: empty window or a NaN maximum); the backward routes dy[o][c] to that one row,
+    dx[i][c] = sum over k ascending with o = inv[k][i] >= 0 of dy[o][c] [arg[o][c] == i]."""
+
+    @staticmethod
+    def forward(ctx, x, nbr, be, mgr):
+        x = x.contiguous()
+        out = be.maxpool_fwd(x, nbr)
+        ctx.save_for_backward(G.maxpool_arg(x, nbr, out), nbr)
+        ctx.mgr, ctx.n_in = mgr, x.shape[0]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        arg, nbr = ctx.saved_tensors
+        inv = ctx.mgr.kernel_map_inverse(nbr, ctx.n_in) if ctx.mgr is not None else G.nbr_invert(nbr, ctx.n_in)
+        return G.maxpool_bwd(dy.contiguous(), arg, inv, ctx.n_in), None, None, None

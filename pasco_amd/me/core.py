@@ -405,8 +405,12 @@ class SparseTensor:
                 coordinate_manager = CoordinateManager(D=3, device=features.device)
             coordinate_map_key, (row2uniq, uniq_rows) = coordinate_manager.insert_and_map(
                 coordinates, tensor_stride)
-            if uniq_rows is not None:  # duplicates: keep the first occurrence
-                features = coordinate_manager.backend().gather_rows(features.contiguous(), uniq_rows)
+            if uniq_rows is not None:  # duplicates: keep the first occurrence (the dropped rows get a zero gradient)
+                if torch.is_grad_enabled() and features.requires_grad:
+                    from .autograd import GatherRowsFunction
+                    features = GatherRowsFunction.apply(features, uniq_rows, coordinate_manager.backend())
+                else:
+                    features = coordinate_manager.backend().gather_rows(features.contiguous(), uniq_rows)
             self.unique_index = uniq_rows
             self.inverse_mapping = row2uniq
         else:
@@ -580,7 +584,12 @@ class SparseTensor:
             assert len(shape) == 5, "shape must be [B, C, X, Y, Z]"
             dims = (int(shape[0]), int(shape[2]), int(shape[3]), int(shape[4]))
         be = self._manager.backend()
-        dense = be.to_dense(self.F.contiguous(), coords, min3, step, dims)
+        feats = self.F
+        if torch.is_grad_enabled() and feats.requires_grad:
+            from .autograd import DenseFunction
+            dense = DenseFunction.apply(feats, coords, min3, step, dims, be)
+        else:
+            dense = be.to_dense(feats.contiguous(), coords, min3, step, dims)
         return dense, min_ret, torch.IntTensor(ts)
 
     # -- training-code helpers (criterion_sparse.py:273-274) ---------------------------------------
@@ -603,7 +612,12 @@ def to_sparse(x: torch.Tensor, format: Optional[str] = None, coordinates=None, d
     assert x.dim() == 5, "to_sparse serves [B, C, X, Y, Z] tensors"
     assert format in (None, "BCXXX"), "only the default BCXXX layout is served"
     be = backend_for(x.device)
-    coords, feats = be.to_sparse(x.contiguous().float())
+    x = x.contiguous().float()
+    if torch.is_grad_enabled() and x.requires_grad:
+        from .autograd import ToSparseFunction
+        coords, feats = ToSparseFunction.apply(x, be)
+    else:
+        coords, feats = be.to_sparse(x)
     mgr = CoordinateManager(D=3, device=x.device)
     key = mgr.insert_unique(coords, 1)
     return SparseTensor(feats, coordinate_map_key=key, coordinate_manager=mgr)

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import backend as B
-from .autograd import ConvFunction, GatherRowsFunction, wants_grad
+from .autograd import ConvFunction, GatherRowsFunction, MaxPoolFunction, wants_grad
 from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple, tensor_version
 
 
@@ -346,7 +346,10 @@ class MinkowskiMaxPooling(MinkowskiModuleBase):
         mgr = x.coordinate_manager
         out_key = mgr.stride(x.coordinate_map_key, self.stride)
         nbr = mgr.kernel_map(x.coordinate_map_key, out_key, self.kernel_size, self.dilation)
-        out = mgr.backend().maxpool_fwd(x.F.contiguous(), nbr)
+        if wants_grad(x.F):
+            out = MaxPoolFunction.apply(x.F, nbr, mgr.backend(), mgr)
+        else:
+            out = mgr.backend().maxpool_fwd(x.F.contiguous(), nbr)
         return SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=mgr)
 
 
