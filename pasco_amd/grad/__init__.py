@@ -1,8 +1,8 @@
 """Training operators of the sparse convolution family (include/pasco_grad.h): the inverse of a neighbour table, the weight
-gradient and the bias gradient; and of the dense <-> rows operators and local max pooling (include/pasco_rowgrad.h).  `host`
-restates them in torch (CPU tensors, the tensor's dtype), `lib` binds the `pg_*` entry points and `rowlib` the `pr_*` ones; the
-functions here serve a tensor from the one its device calls for.  The autograd functions that use them are
-`pasco_amd.me.autograd`."""
+gradient and the bias gradient; of the dense <-> rows operators and local max pooling (include/pasco_rowgrad.h); and of the
+masked cross-attention (include/pasco_attngrad.h).  `host` restates them in torch (CPU tensors, the tensor's dtype), `lib` binds
+the `pg_*` entry points, `rowlib` the `pr_*` ones and `attnlib` the `pa_*` ones; the functions here serve a tensor from the one
+its device calls for.  The autograd functions that use them are `pasco_amd.me.autograd` and `pasco_amd.grad.attention`."""
 from __future__ import annotations
 
 import torch
@@ -57,3 +57,10 @@ def maxpool_bwd(dy: torch.Tensor, arg: torch.Tensor, inv: torch.Tensor, n_in: in
         from .rowlib import rowgrad_lib
         return rowgrad_lib().maxpool_bwd(dy, arg, inv, n_in)
     return host.maxpool_bwd(dy, arg, inv, n_in)
+
+
+def attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q: bool = True, need_k: bool = True, need_v: bool = True):
+    if q.is_cuda:
+        from .attnlib import attn_grad_lib
+        return attn_grad_lib().attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q, need_k, need_v)
+    return host.attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q, need_k, need_v)

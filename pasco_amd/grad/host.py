@@ -1,5 +1,5 @@
-"""Torch restatement of include/pasco_grad.h and include/pasco_rowgrad.h for CPU tensors: index operations and matrix products in
-the tensor's dtype.  The
+"""Torch restatement of include/pasco_grad.h, include/pasco_rowgrad.h and include/pasco_attngrad.h for CPU tensors: index
+operations and matrix products in the tensor's dtype.  The
 CPU tests run on it and `pasco_amd.me.autograd` uses it where the features are not on a GPU.  Same results as the kernels up to
 the order of the fp32 sums."""
 from __future__ import annotations
@@ -103,3 +103,52 @@ def maxpool_bwd(dy: torch.Tensor, arg: torch.Tensor, inv: torch.Tensor, n_in: in
         oc = o.clamp(0, n_out - 1)
         dx = dx + torch.where(have[:, None] & (arg[oc] == rows), dy[oc], torch.zeros_like(dx))
     return dx
+
+
+# ---- include/pasco_attngrad.h -----------------------------------------------------------------------------------------------
+def _attn_allow(bits, any_, B: int, N: int, Q: int, device):
+    """bits int32 [B, N, 4] | None, any int32 [B, 4] | None -> allow bool [B, Q, N] | None by the forward's rules: bit q of a
+    key's word, and a query with no bit in `any` attends everywhere.  Bits at positions >= Q are never looked at."""
+    if bits is None:
+        return None
+    qs = torch.arange(Q, device=device)
+    word, shift = (qs >> 5), (qs & 31).to(torch.int32)
+    allow = ((bits[:, :, word] >> shift) & 1).bool().transpose(1, 2)                    # [B, Q, N]
+    if any_ is not None:
+        allow = allow | ~((any_[:, word] >> shift) & 1).bool()[:, :, None]
+    return allow
+
+
+def attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q: bool = True, need_k: bool = True, need_v: bool = True):
+    """The backward of `attn_cross_fwd` (include/pasco_attngrad.h) in torch, fp32: q [B,H,Q,Dh] (pre-scaled), k / v [B,N,H*Dh],
+    out / dout [B,Q,H*Dh] -> (dq, dk, dv), None where not needed.  One (b, h) at a time: P = softmax(q k^T + mask),
+    delta = sum_d dout out, dV = P^T dout, dS = P (dout v^T - delta), dK = dS^T q, dQ = dS k.  A query with nothing allowed has
+    P = 0 (zero output row, zero dq row)."""
+    B, H, Q, Dh = q.shape
+    N = k.shape[1]
+    allow = _attn_allow(bits, any_, B, N, Q, q.device)
+    dq = torch.zeros_like(q) if need_q else None
+    dk = torch.zeros_like(k) if need_k else None
+    dv = torch.zeros_like(v) if need_v else None
+    for b in range(B):
+        for h in range(H):
+            sl = slice(h * Dh, (h + 1) * Dh)
+            qq, kk, vv, do, o = q[b, h], k[b, :, sl], v[b, :, sl], dout[b, :, sl], out[b, :, sl]
+            s = qq @ kk.t()                                                             # [Q, N]
+            if allow is not None:
+                s = s.masked_fill(~allow[b], float("-inf"))
+            m = s.max(dim=1, keepdim=True).values
+            m = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+            p = torch.exp(s - m)
+            l = p.sum(dim=1, keepdim=True)
+            p = p / torch.where(l > 0, l, torch.ones_like(l))
+            delta = (do @ o.t()).diagonal()[:, None]      # by the product that forms do @ vv.t(): where out == v the two cancel exactly
+            if need_v:
+                dv[b, :, sl] = p.t() @ do
+            if need_q or need_k:
+                ds = p * (do @ vv.t() - delta)
+                if need_k:
+                    dk[b, :, sl] = ds.t() @ qq
+                if need_q:
+                    dq[b, h] = ds @ kk
+    return dq, dk, dv
