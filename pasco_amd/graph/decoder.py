@@ -199,7 +199,8 @@ class DecoderBlock(nn.Module):
         ts = out_key.tensor_stride[0]
         w = conv.kernel
         ver = (w._version, w.data_ptr(), conv.bias._version if conv.bias is not None else -1, ts) + tuple(
-            (t._version, t.data_ptr()) for t in (bn.bn.running_mean, bn.bn.running_var, bn.bn.weight, bn.bn.bias) if t is not None)
+            (t._version, t.data_ptr()) for t in (bn.bn.running_mean, bn.bn.running_var, bn.bn.weight, bn.bn.bias,
+                                                 bn.bn.num_batches_tracked) if t is not None)
         hit = self.__dict__.get("_ph_resize")
         if hit is None or hit[0] != ver:
             with torch.no_grad():

@@ -394,7 +394,9 @@ def fold_bn(bn) -> Tuple[torch.Tensor, torch.Tensor]:
     # ~90 calls per step: the tensors straight from the module's dictionaries (nn.Module.__getattr__ costs ~1 us a name)
     bufs, pars = m._buffers, m._parameters
     rm, rv, w, b = bufs["running_mean"], bufs["running_var"], pars.get("weight"), pars.get("bias")
-    ver = (rm._version, rv._version, w._version if w is not None else -1, b._version if b is not None else -1, rm.device)
+    nbt = bufs.get("num_batches_tracked")     # advanced in place by every training-mode forward, which moves rm / rv inside the op
+    ver = (rm._version, rv._version, w._version if w is not None else -1, b._version if b is not None else -1, rm.device,
+           nbt._version if nbt is not None else -1)
     hit = m.__dict__.get("_ph_folded")
     if hit is not None and hit[0] == ver:
         return hit[1], hit[2]

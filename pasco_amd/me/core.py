@@ -99,6 +99,22 @@ def tensor_version(t: torch.Tensor) -> Optional[int]:
         return None
 
 
+def apply_prologue(raw: torch.Tensor, pending) -> torch.Tensor:
+    """act(raw * scale + shift) of a pending (scale | None, shift | None, act, slope) (`SparseTensor.deferred`) in torch
+    operations."""
+    scale, shift, act, slope = pending
+    y = raw
+    if scale is not None:
+        y = y * scale
+    if shift is not None:
+        y = y + shift
+    if act == 1:
+        y = torch.relu(y)
+    elif act == 2:
+        y = torch.nn.functional.leaky_relu(y, slope)
+    return y
+
+
 def kernel_offsets(kernel_size, tensor_stride, dilation=1, transposed=False) -> List[Tuple[int, int, int]]:
     """Offsets of a hyper-cube kernel in upstream's enumeration: x fastest; odd sizes centred,
     even sizes start at 0.  Scaled by tensor stride * dilation; negated for
@@ -438,17 +454,7 @@ class SparseTensor:
         return out
 
     def _materialise(self) -> None:
-        scale, shift, act, slope = self._pending
-        y = self._F
-        if scale is not None:
-            y = y * scale
-        if shift is not None:
-            y = y + shift
-        if act == 1:
-            y = torch.relu(y)
-        elif act == 2:
-            y = torch.nn.functional.leaky_relu(y, slope)
-        self._F, self._pending = y, None
+        self._F, self._pending = apply_prologue(self._F, self._pending), None
 
     def take_prologue(self):
         """-> (raw features, (scale, shift, act, slope) | None) for a consumer that applies the pending operations itself."""

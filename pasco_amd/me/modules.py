@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import backend as B
 from .autograd import ConvFunction, GatherRowsFunction, MaxPoolFunction, wants_grad
-from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple, tensor_version
+from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple, apply_prologue, tensor_version
 
 
 class MinkowskiModuleBase(nn.Module):
@@ -94,6 +94,8 @@ class _ConvBase(MinkowskiModuleBase):
         out_key, nbr = self._maps(x)
         mgr = x.coordinate_manager
         raw, pending = x.take_prologue()
+        if pending is not None and wants_grad(raw, self.kernel, self.bias):
+            raw, pending = x.F, None          # the backward needs the operand itself: apply what is pending, once, on the tensor
         out = self.conv_rows(mgr.backend(), raw, nbr, mgr.size(out_key), mgr=mgr, prologue=pending)
         return SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=mgr)
 
@@ -108,10 +110,14 @@ class _ConvBase(MinkowskiModuleBase):
         `prologue` = (scale, shift, act, slope) of a deferred BatchNorm / activation in front (SparseTensor.deferred): applied
         to the gathered rows by the launch itself instead of by separate passes over the tensor.
         With autograd enabled and features, kernel or bias requiring grad the same launches run inside
-        `autograd.ConvFunction`, which gives the result its `grad_fn` (backward: include/pasco_grad.h)."""
+        `autograd.ConvFunction`, which gives the result its `grad_fn` (backward: include/pasco_grad.h).  A pending prologue
+        is then applied first (torch operations, differentiable down to the raw rows): the weight gradient needs the operand
+        the products saw, not the raw rows."""
         if torch.is_grad_enabled():
             exact = self.kernel.requires_grad and self.training
-            if prologue is None and wants_grad(feats, self.kernel, self.bias):
+            if wants_grad(feats, self.kernel, self.bias):
+                if prologue is not None:
+                    feats = apply_prologue(feats, prologue)
                 return ConvFunction.apply(feats, self.kernel, self.bias,
                                           lambda f: self._launch(be, f, nbr, n_out, mgr, None, exact), be, nbr, n_out, mgr)
             return self._launch(be, feats, nbr, n_out, mgr, prologue, exact)
@@ -206,7 +212,9 @@ class MinkowskiBatchNorm(nn.Module):
         m = self.bn
         bufs, pars = m._buffers, m._parameters
         rm, rv, w, b = bufs["running_mean"], bufs["running_var"], pars.get("weight"), pars.get("bias")
-        vers = [tensor_version(t) if t is not None else -1 for t in (rm, rv, w, b)]
+        # a training-mode forward updates the running statistics inside the op without moving their version counters; the
+        # module advances num_batches_tracked itself (an in-place add_), so its counter stands for them
+        vers = [tensor_version(t) if t is not None else -1 for t in (rm, rv, w, b, bufs.get("num_batches_tracked"))]
         ver = None if None in vers else tuple(vers) + (rm.device, rm.data_ptr())    # None: inference tensors, fold every call
         hit = self.__dict__.get("_ph_me_folded")
         if ver is None or hit is None or hit[0] != ver:
@@ -230,6 +238,9 @@ class MinkowskiBatchNorm(nn.Module):
                 x.F                        # an activation is pending: it has to be applied before this affine
             scale, shift = self.folded()
             return SparseTensor.deferred(x, scale, shift, B.ACT_NONE, 0.01)
+        if m.training:                     # the running statistics move: no fold made before this call stands for them
+            self.__dict__.pop("_ph_me_folded", None)
+            m.__dict__.pop("_ph_folded", None)
         return _same_map(x, self.bn(x.F))
 
 

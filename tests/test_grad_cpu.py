@@ -10,7 +10,8 @@ import pasco_amd.me as ME
 from pasco_amd.grad import host
 from tests import test_bindings_cpu as tb
 from tests.conv_ref64 import gather_sum64, violations
-from tests.grad_cases import KINDS, make_map, make_module, operands, stack_ratios
+from tests.grad_cases import (KINDS, SLAB_ROWS, WGRAD_CAPPED, WGRAD_CASES, box_coords, make_map, make_module, operands, stack_ratios,
+                              table_out_of_range, wgrad_geometry)
 from tests.grad_ref64 import C_WGRAD, STACK_M, conv_twin, invert_loop, invert_torch, sum_cap, wgrad64
 
 CPU = torch.device("cpu")
@@ -124,6 +125,34 @@ def test_host_wgrad_edges():
     want[3] = torch.outer(x[2], dy[1]) + torch.outer(x[0], dy[4])
     assert torch.allclose(host.conv_wgrad(x, dy, nbr), want, atol=1e-6)
     assert torch.equal(host.colsum(torch.empty(0, 4)), torch.zeros(4))
+
+
+def test_host_wgrad_entries_outside_the_input_are_absent(oracle_registered):
+    m = make_map("same", CPU)
+    bad = table_out_of_range(m["nbr"], m["n_in"])
+    assert int((bad >= m["n_in"]).sum()) > 100 and int((bad == -7).sum()) > 100
+    x, dy = operands(m["n_in"], 12, m["n_out"], 9, CPU)
+    ref, A = wgrad64(x, dy, bad)
+    absent = torch.where((bad >= 0) & (bad < m["n_in"]), bad, torch.full_like(bad, -1))
+    assert torch.equal(wgrad64(x, dy, absent)[0], ref)
+    got = host.conv_wgrad(x, dy, bad)
+    assert bool(((got.double() - ref).abs() <= sum_cap(m["n_out"]) * A + 1e-30).all())
+
+
+def test_wgrad_geometry_restates_the_library_queries():
+    """tests/grad_cases.py `wgrad_geometry` chooses the shapes of the device tests: its slab arithmetic against the library's own
+    host-side queries (nothing is launched), over the case tables."""
+    from pasco_amd.grad.lib import GradLib
+    from pasco_amd.build import build_hip
+    lib = GradLib(build_hip(verbose=False))
+    assert lib.wgrad_slab_rows(27, 32, 32, 1) == SLAB_ROWS
+    natural = box_coords(0).shape[0]
+    for name, kind, cin, cout, rows_of in WGRAD_CASES + [WGRAD_CAPPED[:4] + (lambda R: WGRAD_CAPPED[4],)]:
+        K = 27 if kind == "same" else 8
+        rows = natural if rows_of is None else rows_of(SLAB_ROWS)
+        g = wgrad_geometry(K, cin, cout, rows)
+        assert g["slab_rows"] == lib.wgrad_slab_rows(K, cin, cout, rows), name
+        assert lib.wgrad_workspace_bytes(K, cin, cout, rows) == (0 if g["slabs"] == 1 else g["slabs"] * K * cin * cout * 4), name
 
 
 def _pruning(feats, m, mask):

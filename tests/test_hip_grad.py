@@ -5,7 +5,8 @@ import torch
 
 import pasco_amd.me as ME
 from tests.conv_ref64 import gather_sum64, violations, worst_ratio
-from tests.grad_cases import KINDS, WGRAD_CASES, make_map, make_module, operands, stack_ratios, table_with_rows
+from tests.grad_cases import (COLSUM_ROWS, DGRAD_CASES, KINDS, WGRAD_CAPPED, WGRAD_CASES, WGRAD_MISALIGNED, make_map, make_module,
+                              misaligned, operands, stack_ratios, table_out_of_range, table_with_rows, wgrad_geometry)
 from tests.grad_ref64 import C_WGRAD, STACK_M, invert_torch, sum_cap, wgrad64
 
 pytestmark = pytest.mark.gpu
@@ -49,6 +50,7 @@ def _check_wgrad(lib, x, dy, nbr, what):
     worst = float((err[ok] / A[ok]).max()) if bool(ok.any()) else 0.0
     print(f"wgrad {what}: n_out = {nbr.shape[1]}, worst err / A = {worst:.3e}")
     assert bool(torch.isfinite(got).all())
+    assert bool((err <= sum_cap(nbr.shape[1]) * A + 1e-30).all()), f"{what}: worst err / A = {worst:.3e} above the a-priori cap"
     assert bool((err <= C_WGRAD * A + 1e-30).all()), f"{what}: worst err / A = {worst:.3e}, C_WGRAD = {C_WGRAD:.3e}"
     return got
 
@@ -66,9 +68,44 @@ def test_conv_wgrad_against_fp64(case, lib, dev):
     _check_wgrad(lib, x, dy, nbr, name)
 
 
+def test_conv_wgrad_slab_length_doubled_by_the_workspace_cap(lib, dev):
+    name, kind, cin, cout, rows = WGRAD_CAPPED
+    R = lib.wgrad_slab_rows(27, cin, cout, 1)
+    assert lib.wgrad_slab_rows(27, cin, cout, rows) == 2 * R == wgrad_geometry(27, cin, cout, rows)["slab_rows"]
+    assert lib.wgrad_workspace_bytes(27, cin, cout, rows) == 5 * 27 * cin * cout * 4
+    nbr, n_in = table_with_rows(kind, rows, dev)
+    assert nbr.shape[1] == rows
+    x, dy = operands(n_in, cin, rows, cout, dev)
+    first = _check_wgrad(lib, x, dy, nbr, name)
+    again = lib.conv_wgrad(x, dy, nbr, out=torch.full_like(first, 3.0))
+    assert torch.equal(first, again)                # overwritten, and the same bits
+
+
+@pytest.mark.parametrize("which", WGRAD_MISALIGNED)
+def test_conv_wgrad_base_pointer_not_16_byte_aligned(which, lib, dev):
+    R = lib.wgrad_slab_rows(27, 32, 32, 1)
+    nbr, n_in = table_with_rows("same", R, dev)
+    x, dy = operands(n_in, 32, R, 32, dev)
+    aligned = lib.conv_wgrad(x, dy, nbr)
+    xm, dym = (misaligned(x), dy) if which == "x" else (x, misaligned(dy))
+    got = _check_wgrad(lib, xm, dym, nbr, f"{which} misaligned")
+    assert torch.equal(got, aligned)                # the same values in the same order, whichever loads fetched them
+
+
+def test_conv_wgrad_entries_outside_the_input_are_absent(lib, dev):
+    nbr, n_in = table_with_rows("same", None, dev)
+    bad = table_out_of_range(nbr, n_in)
+    absent = torch.where((bad >= 0) & (bad < n_in), bad, torch.full_like(bad, -1))
+    assert int((bad >= n_in).sum()) > 100 and int((bad == -7).sum()) > 100
+    for cin, cout in ((32, 32), (129, 130)):        # vector and scalar loads
+        x, dy = operands(n_in, cin, nbr.shape[1], cout, dev)
+        got = _check_wgrad(lib, x, dy, bad, f"out-of-range entries {cin}x{cout}")
+        assert torch.equal(got, lib.conv_wgrad(x, dy, absent))
+
+
 def test_conv_wgrad_constant_is_below_the_a_priori_cap(lib):
     R = lib.wgrad_slab_rows(27, 64, 64, 1)
-    assert C_WGRAD < sum_cap(2 * R + 3)           # the largest row count of the case table
+    assert C_WGRAD < sum_cap(2 * R + 3)           # the row count of the three-slab case the constant was calibrated on
 
 
 def test_conv_wgrad_absent_offset_and_no_rows(lib, dev):
@@ -114,9 +151,29 @@ def test_input_gradient_through_conv_function(kind, lib, dev):
     assert not bool(bad.any()), int(bad.sum())
 
 
+@pytest.mark.parametrize("case", DGRAD_CASES, ids=[f"{c[0]}to{c[1]}_{c[2]}" for c in DGRAD_CASES])
+def test_input_gradient_shapes(case, lib, dev):
+    cin, cout, kind = case
+    m = make_map(kind, dev)
+    torch.manual_seed(2)
+    mod = make_module(kind, cin, cout).to(dev).train()
+    g = torch.Generator().manual_seed(6)
+    feats = torch.randn(m["n_in"], cin, generator=g).to(dev).requires_grad_(True)
+    dy = torch.randn(m["n_out"], cout, generator=g).to(dev)
+    out = mod(ME.SparseTensor(feats, coordinate_map_key=m["in_key"], coordinate_manager=m["mgr"]))
+    assert out.F.grad_fn is not None
+    out.F.backward(dy)
+    inv = invert_torch(m["nbr"], m["n_in"])
+    w_t = mod.kernel.detach().transpose(1, 2).contiguous()
+    acc, mag = gather_sum64(dy, w_t, inv, torch.arange(m["n_in"], device=dev))
+    bad = violations(feats.grad, acc, mag, acc.abs())
+    print(f"input gradient {cin} -> {cout} {kind}: worst err / A = {worst_ratio(feats.grad, acc, mag, acc.abs()):.3e}")
+    assert feats.grad.shape == feats.shape and not bool(bad.any()), int(bad.sum())
+
+
 # ---- pg_colsum ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [1, 255, 257, 4099])
-@pytest.mark.parametrize("c", [1, 20, 256])
+@pytest.mark.parametrize("n", [1, 255, 257, 4099, COLSUM_ROWS, COLSUM_ROWS + 1])
+@pytest.mark.parametrize("c", [1, 20, 256, 65])
 def test_colsum(n, c, lib, dev):
     dy = operands(0, 1, n, c, dev, seed=n + c)[1]
     got = lib.colsum(dy)
