@@ -16,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..me.backend import ACT_RELU, MAX_KVOL, backend_for
-from .fused import fold_bn
+from .fused import derived, fold_bn
 
 
 def _conv(c, k):
@@ -71,16 +71,13 @@ class SPCDense3Dv2(nn.Module):
         """Conv3d weight [Cout, Cin, kx, ky, kz] -> [K, Cin, Cout] with K enumerated y fastest, then x, then z - the order of the
         grid's kernel maps (`CBackend.grid_offsets`: the direction in which consecutive sites are consecutive rows)."""
         w = getattr(self, name)[0].weight
-        hit = getattr(self, "_roww_" + name, None)
-        ver = (w._version, w.device)
-        if hit is None or hit[0] != ver:
+
+        def build():
             k = w.shape[2] * w.shape[3] * w.shape[4]
             rw = w.detach().permute(4, 2, 3, 1, 0).reshape(k, w.shape[1], w.shape[0]).contiguous()
-            if k == 1:
-                rw = rw.reshape(w.shape[1], w.shape[0])
-            hit = (ver, rw)
-            object.__setattr__(self, "_roww_" + name, hit)
-        return hit[1]
+            return rw.reshape(w.shape[1], w.shape[0]) if k == 1 else rw
+
+        return derived(self, "_roww_" + name, (w,), None, build)
 
     def _grid_tables(self, dims, device):
         """Site coordinates + neighbour tables per kernel shape, cached per grid shape.  The sites are enumerated Z-MAJOR -
@@ -132,11 +129,8 @@ class SPCDense3Dv2(nn.Module):
             w = self._row_weight(name)
             split = in_split = None
             if fused.conv_precision() == "f16x3" and be.split_supported(w.shape[-2], w.shape[-1]):
-                hit = getattr(self, "_split_" + name, None)
-                if hit is None or hit[0] is not w or hit[1] != fused._PRESPLIT:
-                    hit = (w, fused._PRESPLIT, fused._split_of(w, be))
-                    object.__setattr__(self, "_split_" + name, hit)
-                split = hit[2]
+                # the row weight is itself an entry: a rebuilt one is another object, and this entry follows it
+                split = derived(self, "_split_" + name, (w,), fused._PRESPLIT, lambda: fused._split_of(w, be))
                 if fused._PRESPLIT:
                     if id(x) not in in_splits:
                         in_splits[id(x)] = (x, be.split_rows(x))

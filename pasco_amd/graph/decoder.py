@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import me as ME
+from ..me.core import tensor_version
 from . import fused
 from .blocks import BasicGenerativeDeconvolutionBlock, ResidualBlock, SpatialDropout, run_sequential
 from .fused import ACT_NONE, ACT_RELU
@@ -37,7 +38,10 @@ def _corner(v, coords: torch.Tensor) -> torch.Tensor:
     if torch.is_tensor(v):
         # keyed by stream as well: the cast made on another scene thread's stream may not have run yet when this one reads it
         stream = torch.cuda.current_stream(coords.device).cuda_stream if coords.device.type == "cuda" else 0
-        key = (coords.dtype, coords.device, stream, v._version)
+        ver = tensor_version(v)
+        if ver is None:        # an inference tensor: nothing says whether it was written to, and the cast is one tiny kernel
+            return v.to(device=coords.device, dtype=coords.dtype).reshape(1, 3)
+        key = (coords.dtype, coords.device, stream, ver)       # the entry lives on `v` itself: the object is part of the key
         cache = getattr(v, "_ph_corner", None)
         if cache is not None and key in cache:
             return cache[key]
@@ -198,11 +202,9 @@ class DecoderBlock(nn.Module):
             return self._resize_plain(dec, out_key)
         ts = out_key.tensor_stride[0]
         w = conv.kernel
-        ver = (w._version, w.data_ptr(), conv.bias._version if conv.bias is not None else -1, ts) + tuple(
-            (t._version, t.data_ptr()) for t in (bn.bn.running_mean, bn.bn.running_var, bn.bn.weight, bn.bn.bias,
-                                                 bn.bn.num_batches_tracked) if t is not None)
-        hit = self.__dict__.get("_ph_resize")
-        if hit is None or hit[0] != ver:
+        m = bn.bn
+
+        def build():
             with torch.no_grad():
                 s_, b_ = fused.fold_bn(bn)
                 s64, b64, w64 = s_.double(), b_.double(), w.detach().reshape(c_in + 3, c_out).double()
@@ -213,10 +215,11 @@ class DecoderBlock(nn.Module):
                 idx = torch.arange(self.RESIZE_ROWS, device=w.device, dtype=torch.float64) + self.RESIZE_LO
                 tab = torch.stack([((idx / ts) * s64[c_in + a] + b64[c_in + a])[:, None] * w64[c_in + a][None, :]
                                    for a in range(3)]).float().contiguous()                       # [3, T, c_out]
-            hit = (ver, wf, bias.float().contiguous(), tab)
-            fused.publish(tab)
-            self.__dict__["_ph_resize"] = hit
-        _, wf, bias, tab = hit
+            return wf, bias.float().contiguous(), tab
+
+        # every tensor the three values are made of; `linear_rows` below keys its operand on (wf, bias), the objects of this entry
+        wf, bias, tab = fused.derived(self, "_ph_resize", (w, conv.bias, m.running_mean, m.running_var, m.weight, m.bias,
+                                                           m.num_batches_tracked), ts, build)
         coords = mgr.get_coordinates(out_key)
         out = fused.linear_rows(None, wf, bias, self, "resize", in_split=dec.split,
                                 axis=(tab, coords.contiguous(), self.RESIZE_LO), out=out)

@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from ..me import SparseTensor
+from ..me.core import derived, publish, tensor_version      # noqa: F401  (`derived`: the one cache every entry here goes through)
 from ..me.backend import ACT_LEAKY, ACT_NONE, ACT_RELU
 from ..me.modules import MinkowskiBatchNorm, _ConvBase
 
@@ -166,18 +167,6 @@ def _conv_unfused(x, mod, pro_bn, pro_act, epi_bn, epi_act, epi2_bn, residual, r
     return _module_act(y, res_act, slope)
 
 
-def publish(t):
-    """Call before a tensor derived from the parameters (split weights, folded BatchNorms, composed projections, tables)
-    is stored in a module-wide cache: the cache is read by every stream (scenes in flight each have their own), but the
-    tensor was made by launches on THIS one - the producing stream is drained first, so that no other stream can find the
-    entry before its data exists.  Once per cache entry and parameter version (warm-up), never per step; inside a graph
-    capture nothing may synchronise (the capture's warm-up calls have built the entries already)."""
-    dev = t.device if torch.is_tensor(t) else t
-    if dev.type == "cuda" and not torch.cuda.is_current_stream_capturing():
-        torch.cuda.current_stream(dev).synchronize()
-    return t
-
-
 def _split_of(w, be):
     return be.split_weight_rows(w) if _PRESPLIT else be.split_weight_f16(w)
 
@@ -185,26 +174,29 @@ def _split_of(w, be):
 def split_weight(mod, be):
     """Cached f16 split of a conv module's kernel: (w_split, unscale) for mode 2, (hi, lo, unscale) for mode 1."""
     w = mod.kernel
-    ver = (w._version, w.device, _PRESPLIT)
-    hit = getattr(mod, "_ph_split", None)
-    if hit is None or hit[0] != ver:
-        hit = (ver, _split_of(w, be))
-        publish(w.device)
-        object.__setattr__(mod, "_ph_split", hit)
-    return hit[1]
+    return derived(mod, "_ph_split", (w,), _PRESPLIT, lambda: _split_of(w, be))
 
 
 def split_input(x: SparseTensor, be, ps, pb, pro_act, slope):
     """Pre-split rows of act(x.F * ps + pb), cached on the SparseTensor (several consumers of one tensor with the
     same prologue - e.g. the per-subnet heads - split it once)."""
-    F = x.F if x.F.is_contiguous() else x.F.contiguous()
+    F = x.F
+    if not F.is_contiguous():
+        # the contiguous copy is kept on the tensor too: the operands are keyed by the OBJECT they were made from, and a new copy
+        # per call would neither find the operand of the last one nor let go of it
+        held = x.__dict__.get("_ph_contiguous")
+        if held is None or held[0] is not F or held[2] != tensor_version(F):
+            held = (F, F.contiguous(), tensor_version(F))
+            x.__dict__["_ph_contiguous"] = held
+            x.__dict__.pop("_ph_in_split", None)
+        F = held[1]
     key = _split_key(F, ps, pb, pro_act, slope)
     cache = x.__dict__.setdefault("_ph_in_split", {})
     hit = cache.get(key)
-    if hit is None:
-        hit = be.split_rows(F, pro_scale=ps, pro_shift=pb, pro_act=pro_act, slope=slope)
+    if hit is None or not _split_stands(hit, F, ps, pb):
+        hit = _split_entry(F, ps, pb, be.split_rows(F, pro_scale=ps, pro_shift=pb, pro_act=pro_act, slope=slope))
         cache[key] = hit
-    return hit
+    return hit[0]
 
 
 def gathered_split(x: SparseTensor, rows: torch.Tensor, out_key):
@@ -234,7 +226,7 @@ def split_rows_2d(x2d: torch.Tensor):
 
 def linear_rows(x2d: Optional[torch.Tensor], weight: torch.Tensor, bias, cache_owner, cache_key: str,
                 min_rows: Optional[int] = None, in_split=None, residual: Optional[torch.Tensor] = None,
-                emit: bool = False, want_out: bool = True, axis=None, out: Optional[torch.Tensor] = None):
+                emit: bool = False, want_out: bool = True, axis=None, out: Optional[torch.Tensor] = None, sources=None):
     """y = x @ weight.T + bias for a tall [N, cin] operand (`weight` is an nn.Linear-style [cout, cin] tensor
     or a row slice of one).  Large N on the GPU goes through the convolution kernel as an identity-map k=1
     convolution - the same split-precision MFMA GEMM with fused bias - instead of an fp32 library GEMM;
@@ -245,7 +237,9 @@ def linear_rows(x2d: Optional[torch.Tensor], weight: torch.Tensor, bias, cache_o
     `x2d` may be None when `in_split` (its pre-split operand) is given.
     `emit`: also return the pre-split operand of y for a following linear_rows / batched_rows_matmul -> (y, y_split);
     y_split is None when the split path did not apply, and with `want_out=False` y is None when it did.
-    `out` (optional, contiguous fp32 [N, cout]): the kernel path writes y there (a row slice of a larger tensor)."""
+    `out` (optional, contiguous fp32 [N, cout]): the kernel path writes y there (a row slice of a larger tensor).
+    `sources`: the tensors the cached operand of (`weight`, `bias`) stands for (`derived`) where these are not the long-lived
+    objects themselves: a row slice `w[a:b]` is a new view on every call, its parameter `w` is the source."""
     cout, cin = weight.shape
     n = x2d.shape[0] if x2d is not None else in_split.shape[0]
     dev = x2d.device if x2d is not None else in_split.device
@@ -266,14 +260,11 @@ def linear_rows(x2d: Optional[torch.Tensor], weight: torch.Tensor, bias, cache_o
             out.copy_(y)
             y = out
         return (y, None) if emit else y
-    ver = (weight._version, weight.device, weight.data_ptr(), _PRESPLIT)
-    hit = cache_owner.__dict__.get("_ph_lin_" + cache_key)
-    if hit is None or hit[0] != ver:
+    def build():
         wt = weight.detach().t().contiguous()                     # [cin, cout]
-        hit = (ver, wt, _split_of(wt, be), bias.detach().contiguous() if bias is not None else None)
-        publish(wt)
-        cache_owner.__dict__["_ph_lin_" + cache_key] = hit
-    _, wt, split, b = hit
+        return wt, _split_of(wt, be), bias.detach().contiguous() if bias is not None else None
+
+    wt, split, b = derived(cache_owner, "_ph_lin_" + cache_key, (weight, bias) if sources is None else sources, _PRESPLIT, build)
     do_emit = emit and _PRESPLIT and cout % 32 == 0
     out = be.conv_fwd(None if (x2d is None) else x2d.contiguous(), wt, None, n,
                       xshape=(n, cin) if x2d is None else None, bias=b, split=split,
@@ -323,16 +314,14 @@ def linear_bn_act(x2d: Optional[torch.Tensor], lin: nn.Linear, *, pro_bn=None, e
         ps, pb = fold_bn(pro_bn)
     if epi_bn is not None:
         es, eb = fold_bn(epi_bn)
-    w = lin.weight
-    ver = (w._version, w.device, w.data_ptr(), _PRESPLIT, conv_precision())
-    hit = lin.__dict__.get("_ph_lin_w")
-    if hit is None or hit[0] != ver:
+    w, precision = lin.weight, conv_precision()
+
+    def build():
         wt = w.detach().t().contiguous()                          # [cin, cout]
-        split = _split_of(wt, be) if (conv_precision() == "f16x3" and be.split_supported(cin, cout)) else None
-        hit = (ver, wt, split, lin.bias.detach().contiguous() if lin.bias is not None else None)
-        publish(wt)
-        lin.__dict__["_ph_lin_w"] = hit
-    _, wt, split, b = hit
+        split = _split_of(wt, be) if (precision == "f16x3" and be.split_supported(cin, cout)) else None
+        return wt, split, lin.bias.detach().contiguous() if lin.bias is not None else None
+
+    wt, split, b = derived(lin, "_ph_lin_w", (w, lin.bias), (_PRESPLIT, precision), build)
     do_emit = emit and split is not None and _PRESPLIT and cout % 32 == 0
     assert x2d is not None or (split is not None and _PRESPLIT), "a pre-split operand needs the split path"
     out = be.conv_fwd(None if x2d is None else x2d.contiguous(), wt, None, n, xshape=(n, cin) if x2d is None else None,
@@ -387,7 +376,7 @@ def batched_rows_matmul(x: Optional[torch.Tensor], w: Optional[torch.Tensor], x_
 
 
 def fold_bn(bn) -> Tuple[torch.Tensor, torch.Tensor]:
-    """BatchNorm (eval) -> (scale, shift) with y = x * scale + shift. Cached per module version."""
+    """BatchNorm (eval) -> (scale, shift) with y = x * scale + shift.  Cached (`derived`) on the five tensors it reads."""
     m = bn.bn if isinstance(bn, MinkowskiBatchNorm) else bn
     assert isinstance(m, nn.modules.batchnorm._BatchNorm)
     assert not m.training, "fused graph serves inference (module.eval()) only"
@@ -395,19 +384,15 @@ def fold_bn(bn) -> Tuple[torch.Tensor, torch.Tensor]:
     bufs, pars = m._buffers, m._parameters
     rm, rv, w, b = bufs["running_mean"], bufs["running_var"], pars.get("weight"), pars.get("bias")
     nbt = bufs.get("num_batches_tracked")     # advanced in place by every training-mode forward, which moves rm / rv inside the op
-    ver = (rm._version, rv._version, w._version if w is not None else -1, b._version if b is not None else -1, rm.device,
-           nbt._version if nbt is not None else -1)
-    hit = m.__dict__.get("_ph_folded")
-    if hit is not None and hit[0] == ver:
-        return hit[1], hit[2]
-    with torch.no_grad():
-        inv = torch.rsqrt(m.running_var.float() + m.eps)
-        scale = inv * (m.weight.float() if m.weight is not None else 1.0)
-        shift = (m.bias.float() if m.bias is not None else 0.0) - m.running_mean.float() * scale
-        scale, shift = scale.contiguous(), shift.contiguous()
-    publish(scale)
-    m._ph_folded = (ver, scale, shift)
-    return scale, shift
+
+    def build():
+        with torch.no_grad():
+            inv = torch.rsqrt(rv.float() + m.eps)
+            scale = inv * (w.float() if w is not None else 1.0)
+            shift = (b.float() if b is not None else 0.0) - rm.float() * scale
+            return scale.contiguous(), shift.contiguous()
+
+    return derived(m, "_ph_folded", (rm, rv, w, b, nbt), None, build)
 
 
 class SplitRows:
@@ -422,8 +407,18 @@ class SplitRows:
 
 
 def _split_key(F, ps, pb, pro_act, slope):
-    return (F.data_ptr(), F._version, None if ps is None else ps.data_ptr(), None if pb is None else pb.data_ptr(),
-            pro_act, float(slope) if pro_act == ACT_LEAKY else 0.0)
+    """Key of an operand kept on its SparseTensor: the tensor OBJECTS it was made from (an activation made under
+    torch.inference_mode() has no version counter, and an address can be handed out again) and the prologue's settings.  The
+    entry holds those objects (`_split_entry`), so an id() in a key always names a live tensor."""
+    return (id(F), id(ps), id(pb), pro_act, float(slope) if pro_act == ACT_LEAKY else 0.0)
+
+
+def _split_entry(F, ps, pb, split):
+    return (split, F, ps, pb, tensor_version(F))
+
+
+def _split_stands(hit, F, ps, pb) -> bool:
+    return hit[1] is F and hit[2] is ps and hit[3] is pb and hit[4] == tensor_version(F)
 
 
 def conv(x: SparseTensor, mod: _ConvBase, *, pro_bn=None, pro_act: int = ACT_NONE, epi_bn=None,
@@ -507,8 +502,9 @@ def conv(x: SparseTensor, mod: _ConvBase, *, pro_bn=None, pro_act: int = ACT_NON
         return SplitRows(out_split, mod.out_channels, out_key, mgr)
     y = SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=mgr)
     # key it the way the next conv's split_input will look it up (a leaky prologue would use this launch's slope)
-    y.__dict__.setdefault("_ph_in_split", {})[_split_key(y.F, emit[0], emit[1], emit[2], slope)] = out_split
+    y.__dict__.setdefault("_ph_in_split", {})[_split_key(y.F, emit[0], emit[1], emit[2], slope)] = \
+        _split_entry(y.F, emit[0], emit[1], out_split)
     return y
 
 
-__all__ = ["fold_bn", "conv", "set_conv_precision", "conv_precision", "precision_override", "optimistic", "optimistic_override", "set_fusion", "fusion", "linear_rows", "split_rows_2d", "gathered_split", "batched_rows_matmul", "prepare_batched_weights", "linear_bn_act", "ACT_NONE", "ACT_RELU", "ACT_LEAKY"]
+__all__ = ["fold_bn", "derived", "conv", "set_conv_precision", "conv_precision", "precision_override", "optimistic", "optimistic_override", "set_fusion", "fusion", "linear_rows", "split_rows_2d", "gathered_split", "batched_rows_matmul", "prepare_batched_weights", "linear_bn_act", "ACT_NONE", "ACT_RELU", "ACT_LEAKY"]

@@ -27,6 +27,7 @@ import torch.nn.functional as F
 
 from .. import me as ME
 from ..me.backend import backend_for
+from ..me.core import tensor_version
 from . import fused as fused_mod
 from .fused import batched_rows_matmul, linear_rows, prepare_batched_weights, split_rows_2d
 
@@ -231,8 +232,9 @@ class CrossAttentionLayer(nn.Module):
             kv_split = feats_split
             if kv_split is None and kv2.shape[0] >= fused_mod.MIN_ROWS_LINEAR:
                 kv_split = split_rows_2d(kv2)                                     # one operand split for K and V
-        kk = linear_rows(kv2, w[D:2 * D], b[D:2 * D], self, "k", in_split=kv_split).view(B, N, D)
-        vv = linear_rows(kv2, w[2 * D:], b[2 * D:], self, "v", in_split=kv_split).view(B, N, D)
+        # the row slices are new views on every call: the entries stand for the parameters themselves
+        kk = linear_rows(kv2, w[D:2 * D], b[D:2 * D], self, "k", in_split=kv_split, sources=(w, b)).view(B, N, D)
+        vv = linear_rows(kv2, w[2 * D:], b[2 * D:], self, "v", in_split=kv_split, sources=(w, b)).view(B, N, D)
         qq = qq.view(B, Q, H, D // H).transpose(1, 2)
         if mask_bits is not None:
             be = backend_for(q.device)
@@ -277,23 +279,21 @@ class CrossAttentionLayer(nn.Module):
         (Products in fp64, rounded once: the composed map is the same linear map as the sequence, to fp32 rounding.)"""
         mha = self.multihead_attn
         w, b = mha.in_proj_weight, mha.in_proj_bias
-        ver = tuple((p._version, p.data_ptr()) for p in (w, b, lin.weight, lin.bias)) + (tab.data_ptr(),)
-        hit = self.__dict__.get("_ph_composed")
-        if hit is not None and hit[0] == ver:
-            return hit[1]
         D = w.shape[1]
         f = tab.shape[1]
-        out = {}
-        with torch.no_grad():
-            wp, bp, t64 = lin.weight.double(), lin.bias.double(), tab.double()
-            for name, sl in (("k", slice(D, 2 * D)), ("v", slice(2 * D, 3 * D))):
-                wx, bx = w[sl].double(), b[sl].double()
-                out["w" + name] = (wx @ wp).float().contiguous()
-                out["b" + name] = (wx @ bp + bx).float().contiguous()
-                out["t" + name] = torch.stack([t64 @ wx[:, a * f:(a + 1) * f].t() for a in range(3)]).float().contiguous()
-        fused_mod.publish(w)
-        self.__dict__["_ph_composed"] = (ver, out)
-        return out
+
+        def build():
+            out = {}
+            with torch.no_grad():
+                wp, bp, t64 = lin.weight.double(), lin.bias.double(), tab.double()
+                for name, sl in (("k", slice(D, 2 * D)), ("v", slice(2 * D, 3 * D))):
+                    wx, bx = w[sl].double(), b[sl].double()
+                    out["w" + name] = (wx @ wp).float().contiguous()
+                    out["b" + name] = (wx @ bp + bx).float().contiguous()
+                    out["t" + name] = torch.stack([t64 @ wx[:, a * f:(a + 1) * f].t() for a in range(3)]).float().contiguous()
+            return out
+
+        return fused_mod.derived(self, "_ph_composed", (w, b, lin.weight, lin.bias, tab), None, build)
 
 
     def composed_feat(self, lin: nn.Linear, pe: "PositionEmbeddingSineSparse", exp2: int):
@@ -305,13 +305,15 @@ class CrossAttentionLayer(nn.Module):
         A = W_k W_p, B = W_v W_p (the level's input projection `lin` composed with the K / V projections); the position rows
         tab[t] W^T of an axis are tab_far W^T + [t == 0] D0 + eps_t G W^T (`PositionEmbeddingSineSparse.angle_model`)."""
         mha = self.multihead_attn
+        w = mha.in_proj_weight
+        sources = (w, mha.in_proj_bias, mha.out_proj.weight, mha.out_proj.bias, lin.weight, lin.bias, pe.table(w.device))
+        return fused_mod.derived(self, "_ph_composed_feat", sources, exp2, lambda: self._compose_feat(lin, pe))
+
+    def _compose_feat(self, lin: nn.Linear, pe: "PositionEmbeddingSineSparse"):
+        mha = self.multihead_attn
         w, b = mha.in_proj_weight, mha.in_proj_bias
         wo, bo = mha.out_proj.weight, mha.out_proj.bias
         tab = pe.table(w.device)
-        ver = tuple((p._version, p.data_ptr()) for p in (w, b, wo, bo, lin.weight, lin.bias)) + (tab.data_ptr(), exp2)
-        hit = self.__dict__.get("_ph_composed_feat")
-        if hit is not None and hit[0] == ver:
-            return hit[1]
         D = w.shape[1]
         H = self.nhead
         dh = D // H
@@ -349,9 +351,7 @@ class CrossAttentionLayer(nn.Module):
             co = cv @ wo.double().t() + bo.double()
             out = dict(w2=w2.float().contiguous(), b2=b2.float().contiguous(), mvo=mvo.float().contiguous(),
                        co=co.float().contiguous(), E=E)
-        fused_mod.publish(w)       # the cache serves every stream, the tensors were made on this one
-        self.__dict__["_ph_composed_feat"] = (ver, out)
-        return out
+        return out       # published by `derived` (the cache serves every stream, the tensors were made on this one)
 
     def attend_feat(self, q_embed, comp, x_split, aug, n: int, query_pos, mask_bits):
         """The layer on the level's feature operand (ph_attn_cross_feat): keys and values are never formed."""
@@ -534,7 +534,22 @@ class TransformerPredictorV2(nn.Module):
         return "graph"
 
     def param_versions(self):
-        return tuple((p._version, p.data_ptr()) for p in self.parameters())
+        """What a captured graph is valid for: it bakes in the ADDRESS of every parameter it reads, so the storage address stays
+        in the key beside the version counter (None for a parameter made under torch.inference_mode())."""
+        return tuple((tensor_version(p), p.data_ptr()) for p in self.parameters())
+
+    def __getstate__(self):
+        """copy.deepcopy / pickle: the captured graphs (and a recorded capture failure) belong to this object's parameter
+        addresses and streams and cannot be copied; the copy captures its own on its first call."""
+        state = super().__getstate__()
+        state.pop("_qgraphs", None)
+        state.pop("_qgraph_broken", None)
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        if _PREDICTORS is not None:
+            _PREDICTORS.add(self)          # `release_stream_graphs` walks the live predictors: the copy is one
 
     _QGRAPH_MAX = 48     # captured graphs kept per module (4 per shape and stream; a few shapes, a few streams); oldest evicted
 
@@ -545,7 +560,8 @@ class TransformerPredictorV2(nn.Module):
         graphs = self.__dict__.setdefault("_qgraphs", {})
         # a captured graph bakes in the ADDRESSES of every parameter it reads: the key carries version and storage
         # address of each (load_state_dict(assign=True), .cpu().cuda() round trips, param.data = ... change the
-        # address without bumping the version)
+        # address without bumping the version).  The captured launches read the parameters themselves - the tensors
+        # derived from them (`fused.derived`) are used outside the capture - so same addresses means a valid graph
         # (`vers` from the caller: forward() takes it once for its four calls - walking the module tree costs ~0.2 ms)
         if vers is None:
             vers = self.param_versions()
@@ -576,8 +592,12 @@ class TransformerPredictorV2(nn.Module):
         return out, oc.clone(), me, prepared
 
     def _capture_query_step(self, layer, output, query_embed, want_operand):
-        x = output.detach().clone()
-        qe = query_embed.detach().clone()
+        # the static inputs are written in place before every replay, in whatever mode that call runs: made under
+        # torch.inference_mode() they would be inference tensors, which a later torch.no_grad() call may not write to
+        with torch.inference_mode(False):
+            x, qe = torch.empty_like(output), torch.empty_like(query_embed)
+        x.copy_(output)
+        qe.copy_(query_embed)
         be = backend_for(output.device)
         # the captured launches report into the status word of the stream the graph will be replayed on (this one)
         with be.pin_status(output.device):

@@ -624,7 +624,10 @@ class CBackend:
         key = ("status",) + self._stream_key(torch.device(device))
         t = self._ws.get(key)
         if t is None:
-            t = torch.zeros(2, dtype=torch.int32, device=device)
+            # cleared in place by every later `check_status`: a pair first made under torch.inference_mode() would be an
+            # inference tensor, which no call outside that mode may write to
+            with torch.inference_mode(False):
+                t = torch.zeros(2, dtype=torch.int32, device=device)
             self._ws[key] = t
         return t
 

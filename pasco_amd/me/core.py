@@ -93,10 +93,52 @@ class _CoordMap:
 def tensor_version(t: torch.Tensor) -> Optional[int]:
     """`t._version`, or None for an inference tensor (made under torch.inference_mode(): it has no version counter, reading it
     raises).  Caches keyed on it treat None as "cannot tell whether it changed"."""
-    try:
-        return t._version
-    except RuntimeError:
-        return None
+    return None if t.is_inference() else t._version
+
+
+def publish(t):
+    """Call before a tensor derived from the parameters (split weights, folded BatchNorms, composed projections, tables)
+    is stored in a module-wide cache: the cache is read by every stream (scenes in flight each have their own), but the
+    tensor was made by launches on THIS one - the producing stream is drained first, so that no other stream can find the
+    entry before its data exists.  Once per cache entry and parameter version (warm-up), never per step; inside a graph
+    capture nothing may synchronise (the capture's warm-up calls have built the entries already)."""
+    dev = t.device if torch.is_tensor(t) else t
+    if dev.type == "cuda" and not torch.cuda.is_current_stream_capturing():
+        torch.cuda.current_stream(dev).synchronize()
+    return t
+
+
+def derived(owner, name: str, sources, extra, build, identity_suffices: bool = True):
+    """The one cache of tensors derived from parameters and buffers: `build()`'s value, kept in
+    `owner.__dict__[name]` as (value, sources, versions, key) and handed back while it still stands for its sources.
+
+    `sources`: EVERY tensor the value was computed from (the bias and the BatchNorm tensors as well as the weight; None for an
+    absent one).  The entry keeps the tensors themselves and is valid only while each source is the same object (`is`) at the
+    same version counter: a replaced parameter (`load_state_dict(assign=True)`, a new nn.Parameter) is another object whatever
+    its counter says - an assigned tensor brings the counter of its source, 0 for a loaded file - and an in-place write
+    (`optimizer.step()`, `load_state_dict`, `copy_`) moves the counter.  Holding the source also keeps its address from being
+    handed to another tensor while the entry lives.  An inference tensor (made under torch.inference_mode()) has no counter
+    (`tensor_version` is None): for it identity alone decides, so an in-place write to such a parameter is not seen
+     - the fused graph's choice, ~100 weight splits per step otherwise.  `identity_suffices=False` (the
+    plain `pasco_amd.me` modules, one small entry each): such a source cannot be vouched for, the value is built on every call.
+    `extra`: the settings the value depends on besides (operand layout, precision, tensor stride, operand scale); the device of
+    the first source joins it (`module.cuda()` moves a parameter's storage under the same object and counter).
+    A miss builds the value, drains the producing stream (`publish`) and replaces the entry."""
+    dev = sources[0].device
+    hit = owner.__dict__.get(name)
+    if hit is not None and hit[3] == (extra, dev):
+        for s, held, ver in zip(sources, hit[1], hit[2]):
+            if s is not held:
+                break
+            if s is not None and (tensor_version(s) != ver or (ver is None and not identity_suffices)):
+                break
+        else:
+            return hit[0]
+    value = build()
+    publish(dev)
+    sources = tuple(sources)
+    owner.__dict__[name] = (value, sources, tuple(None if s is None else tensor_version(s) for s in sources), (extra, dev))
+    return value
 
 
 def apply_prologue(raw: torch.Tensor, pending) -> torch.Tensor:

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import backend as B
 from .autograd import ConvFunction, GatherRowsFunction, MaxPoolFunction, wants_grad
-from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple, apply_prologue, tensor_version
+from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple, apply_prologue, derived
 
 
 class MinkowskiModuleBase(nn.Module):
@@ -135,22 +135,16 @@ class _ConvBase(MinkowskiModuleBase):
             pro = dict(pro_scale=ps, pro_shift=pb, pro_act=pact, slope=pslope)
         if n_out == 0 or _ME_CONV != "guarded" or not be.split_supported(self.in_channels, self.out_channels) or exact:
             return be.conv_fwd(feats, kernel, nbr, n_out, bias=bias, **pro)
-        w = self.kernel
-        v = tensor_version(w)         # None: a parameter made under torch.inference_mode() - no version counter, split every call
-        ver = None if v is None else (v, w.data_ptr(), w.device)
-        hit = self.__dict__.get("_ph_me_split")
-        if ver is None or hit is None or hit[0] != ver:
-            hit = (ver, be.split_weight_rows(kernel))
-            if w.is_cuda and not torch.cuda.is_current_stream_capturing():
-                torch.cuda.current_stream(w.device).synchronize()     # the cache serves every stream (fused.publish)
-            self.__dict__["_ph_me_split"] = hit if ver is not None else None
+        # the same cache, under the same rule, as the fused graph's entries (`derived`: valid while the kernel is the same
+        # object at the same version counter); a kernel made under torch.inference_mode() has no counter: split every call
+        w_split = derived(self, "_ph_me_split", (self.kernel,), None, lambda: be.split_weight_rows(kernel), identity_suffices=False)
         flag = torch.zeros(1, dtype=torch.int32, device=feats.device)
         xs = be.split_rows(feats, status=flag, **pro)
         win = None
         if mgr is not None and nbr is not None and nbr.shape[0] == 27 and 33 <= self.out_channels <= 64 and \
                 n_out >= ME_MIN_ROWS_WINDOWS and be.device_type == "cuda":
             win = mgr.kernel_windows(nbr)       # LDS-window tables of the map (cached by the manager): k_conv_wop2
-        out = be.conv_fwd(feats, kernel, nbr, n_out, bias=bias, split=hit[1], in_split=xs, status=flag, win=win)
+        out = be.conv_fwd(feats, kernel, nbr, n_out, bias=bias, split=w_split, in_split=xs, status=flag, win=win)
         be.conv_fwd(feats, kernel, nbr, n_out, bias=bias, out=out, exact_if=flag, **pro)
         return out
 
@@ -214,19 +208,14 @@ class MinkowskiBatchNorm(nn.Module):
         rm, rv, w, b = bufs["running_mean"], bufs["running_var"], pars.get("weight"), pars.get("bias")
         # a training-mode forward updates the running statistics inside the op without moving their version counters; the
         # module advances num_batches_tracked itself (an in-place add_), so its counter stands for them
-        vers = [tensor_version(t) if t is not None else -1 for t in (rm, rv, w, b, bufs.get("num_batches_tracked"))]
-        ver = None if None in vers else tuple(vers) + (rm.device, rm.data_ptr())    # None: inference tensors, fold every call
-        hit = self.__dict__.get("_ph_me_folded")
-        if ver is None or hit is None or hit[0] != ver:
+        def build():
             with torch.no_grad():
                 scale = torch.rsqrt(rv.float() + m.eps) * (w.float() if w is not None else 1.0)
                 shift = (b.float() if b is not None else 0.0) - rm.float() * scale
-                scale, shift = scale.contiguous(), shift.contiguous()
-            if rm.is_cuda and not torch.cuda.is_current_stream_capturing():
-                torch.cuda.current_stream(rm.device).synchronize()       # the cache serves every stream
-            hit = (ver, scale, shift)
-            self.__dict__["_ph_me_folded"] = hit
-        return hit[1], hit[2]
+                return scale.contiguous(), shift.contiguous()
+
+        # inference tensors have no counter: fold every call
+        return derived(self, "_ph_me_folded", (rm, rv, w, b, bufs.get("num_batches_tracked")), None, build, identity_suffices=False)
 
     def forward(self, x: SparseTensor) -> SparseTensor:
         m = self.bn
