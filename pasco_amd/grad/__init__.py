@@ -1,8 +1,9 @@
 """Training operators of the sparse convolution family (include/pasco_grad.h): the inverse of a neighbour table, the weight
 gradient and the bias gradient; of the dense <-> rows operators and local max pooling (include/pasco_rowgrad.h); and of the
-masked cross-attention (include/pasco_attngrad.h).  `host` restates them in torch (CPU tensors, the tensor's dtype), `lib` binds
-the `pg_*` entry points, `rowlib` the `pr_*` ones and `attnlib` the `pa_*` ones; the functions here serve a tensor from the one
-its device calls for.  The autograd functions that use them are `pasco_amd.me.autograd` and `pasco_amd.grad.attention`."""
+masked cross-attention (include/pasco_attngrad.h); and the matcher and mask losses (include/pasco_match.h).  `host` restates them
+in torch (CPU tensors, the tensor's dtype), `lib` binds the `pg_*` entry points, `rowlib` the `pr_*` ones, `attnlib` the `pa_*`
+ones and `matchlib` the `pm_*` ones; the functions here serve a tensor from the one its device calls for.  The autograd
+functions that use them are `pasco_amd.me.autograd`, `pasco_amd.grad.attention` and `pasco_amd.grad.criterion`."""
 from __future__ import annotations
 
 import torch
@@ -64,3 +65,24 @@ def attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q: bool = True, need_k: 
         from .attnlib import attn_grad_lib
         return attn_grad_lib().attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q, need_k, need_v)
     return host.attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q, need_k, need_v)
+
+
+def target_pack(masks, unknown, coords, origin=(0, 0, 0)):
+    if coords.is_cuda:
+        from .matchlib import match_lib
+        return match_lib().target_pack(masks, unknown, coords, origin)
+    return host.target_pack(masks, unknown, coords, origin)
+
+
+def pair_sums(logits, tbits, flags, flag_bit: int, t: int):
+    if logits.is_cuda:
+        from .matchlib import match_lib
+        return match_lib().pair_sums(logits, tbits, flags, flag_bit, t)
+    return host.pair_sums(logits, tbits, flags, flag_bit, t)
+
+
+def mask_loss_bwd(logits, tbits, flags, tgt_of_query, coef, t: int):
+    if logits.is_cuda:
+        from .matchlib import match_lib
+        return match_lib().mask_loss_bwd(logits, tbits, flags, tgt_of_query, coef, t)
+    return host.mask_loss_bwd(logits, tbits, flags, tgt_of_query, coef, t)

@@ -152,3 +152,121 @@ def attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q: bool = True, need_k: 
                 if need_q:
                     dq[b, h] = ds @ kk
     return dq, dk, dv
+
+
+# ---- include/pasco_match.h --------------------------------------------------------------------------------------------------
+def target_bits(tbits: torch.Tensor, t: int) -> torch.Tensor:
+    """tbits int32 [N, 4] -> bool [N, T]: bit k of a row's 128-bit word.  Bits at positions >= T are never looked at."""
+    ks = torch.arange(t, device=tbits.device)
+    return ((tbits[:, ks >> 5] >> (ks & 31).to(torch.int32)) & 1).bool()
+
+
+def target_pack(masks: torch.Tensor, unknown, coords: torch.Tensor, origin=(0, 0, 0)):
+    """pm_target_pack in torch: masks uint8 [T,X,Y,Z], unknown uint8 [X,Y,Z] | None, coords int32 [N,4] -> (tbits int32 [N,4],
+    flags uint8 [N], oob int32 [1])."""
+    t, dx, dy, dz = masks.shape
+    n = coords.shape[0]
+    c = coords[:, 1:].long() - torch.as_tensor([int(o) for o in origin], dtype=torch.int64, device=coords.device)
+    inside = ((c >= 0) & (c < torch.as_tensor([dx, dy, dz], device=coords.device))).all(dim=1)
+    cc = torch.where(inside[:, None], c, torch.zeros_like(c))
+    idx = (cc[:, 0] * dy + cc[:, 1]) * dz + cc[:, 2]
+    tgt = (masks.reshape(t, -1)[:, idx] != 0).t() & inside[:, None]                     # [N, T]
+    known = inside if unknown is None else inside & (unknown.reshape(-1)[idx] == 0)
+    words = torch.zeros((n, 4), dtype=torch.int64, device=coords.device)
+    for k in range(t):
+        words[:, k >> 5] |= tgt[:, k].long() << (k & 31)
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+    flags = (known.to(torch.uint8) | ((known & tgt.any(dim=1)).to(torch.uint8) << 1)).to(torch.uint8)
+    oob = (~inside).sum().to(torch.int32).reshape(1)
+    return words, flags, oob
+
+
+def _mask_terms(x: torch.Tensor):
+    """-> (p, 1 - p, softplus(x), softplus(-x)), none of which overflows or cancels for a finite x."""
+    e = torch.exp(-x.abs())
+    inv = 1.0 / (1.0 + e)
+    pos = x >= 0
+    p = torch.where(pos, inv, e * inv)
+    omp = torch.where(pos, e * inv, inv)
+    l = torch.log1p(e)
+    return p, omp, x.clamp(min=0) + l, (-x).clamp(min=0) + l
+
+
+def pair_sums(logits: torch.Tensor, tbits: torch.Tensor, flags: torch.Tensor, flag_bit: int, t: int):
+    """pm_pair_sums in torch, in the dtype of `logits`: -> (focal_sum [Q,T], dice [Q,T], stats [Q,T,3], count int32 [1]) over the
+    rows whose flag bit `flag_bit` is set."""
+    q = logits.shape[1]
+    on = ((flags >> flag_bit) & 1).bool()
+    x = logits[on]
+    tgt = target_bits(tbits[on], t).to(logits.dtype)
+    p, omp, sp, sn = _mask_terms(x)
+    fp = 0.25 * omp * omp * sn
+    fn = 0.75 * p * p * sp
+    focal_sum = (fp - fn).t() @ tgt + fn.sum(dim=0)[:, None]
+    inter = p.t() @ tgt
+    psum = p.sum(dim=0)[:, None].expand(q, t)
+    tsum = tgt.sum(dim=0)[None, :].expand(q, t)
+    dice = 1 - (2 * inter + 1) / (psum + tsum + 1)
+    stats = torch.stack([inter, psum, tsum], dim=2).contiguous()
+    return focal_sum, dice, stats, on.sum().to(torch.int32).reshape(1)
+
+
+def mask_loss_bwd(logits: torch.Tensor, tbits: torch.Tensor, flags: torch.Tensor, tgt_of_query: torch.Tensor,
+                  coef: torch.Tensor, t: int) -> torch.Tensor:
+    """pm_mask_loss_bwd in torch: dlogits [N,Q]; exactly 0 in unmatched columns and unknown rows."""
+    matched = (tgt_of_query >= 0) & (tgt_of_query < t)
+    known = (flags & 1).bool()
+    y = torch.gather(target_bits(tbits, t), 1, tgt_of_query.clamp(0, t - 1).long()[None, :].expand(logits.shape[0], -1))
+    p, omp, sp, sn = _mask_terms(logits)
+    dfp = -0.25 * omp * omp * (2 * p * sn + omp)
+    dfn = 0.75 * p * p * (2 * omp * sp + p)
+    c, a, b = coef[:, 0][None, :], coef[:, 1][None, :], coef[:, 2][None, :]
+    g = c * torch.where(y, dfp, dfn) + p * omp * torch.where(y, a + b, b)
+    return torch.where(known[:, None] & matched[None, :], g, torch.zeros_like(g))
+
+
+def assign(cost: torch.Tensor):
+    """pm_assign in torch (the method of csrc/pm_assign.h): cost [Q,T] -> (row int64 [K], col int64 [K]), K = min(Q, T), rows
+    ascending.  A non-finite cost is refused."""
+    c = cost.detach().to(torch.float64).cpu()
+    q, t = c.shape
+    if q == 0 or t == 0:
+        return torch.zeros(0, dtype=torch.int64), torch.zeros(0, dtype=torch.int64)
+    if not bool(torch.isfinite(c).all()):
+        raise RuntimeError(f"assign: the {q} x {t} cost matrix has a non-finite entry")
+    tr = q > t
+    if tr:
+        c = c.t()
+    n, m = c.shape
+    inf = float("inf")
+    u, v = torch.zeros(n + 1, dtype=torch.float64), torch.zeros(m + 1, dtype=torch.float64)
+    p, way = [0] * (m + 1), [0] * (m + 1)
+    for i in range(1, n + 1):
+        p[0] = i
+        j0 = 0
+        minv = torch.full((m + 1,), inf, dtype=torch.float64)
+        used = torch.zeros(m + 1, dtype=torch.bool)
+        while True:
+            used[j0] = True
+            i0 = p[j0]
+            cur = c[i0 - 1] - u[i0] - v[1:]
+            better = (cur < minv[1:]) & ~used[1:]
+            minv[1:] = torch.where(better, cur, minv[1:])
+            for j in torch.nonzero(better).flatten().tolist():
+                way[j + 1] = j0
+            free = torch.where(used[1:], torch.full_like(cur, inf), minv[1:])
+            delta = float(free.min())
+            j1 = int(torch.nonzero(free == delta)[0]) + 1           # the first minimum, as the C++ loop finds it
+            for j in torch.nonzero(used).flatten().tolist():
+                u[p[j]] += delta
+                v[j] -= delta
+            minv = torch.where(used, minv, minv - delta)
+            j0 = j1
+            if p[j0] == 0:
+                break
+        while j0 != 0:
+            j1 = way[j0]
+            p[j0] = p[j1]
+            j0 = j1
+    pairs = sorted((j - 1, p[j] - 1) if tr else (p[j] - 1, j - 1) for j in range(1, m + 1) if p[j] != 0)
+    return (torch.tensor([a for a, _ in pairs], dtype=torch.int64), torch.tensor([b for _, b in pairs], dtype=torch.int64))
