@@ -270,3 +270,89 @@ def assign(cost: torch.Tensor):
             j0 = j1
     pairs = sorted((j - 1, p[j] - 1) if tr else (p[j] - 1, j - 1) for j in range(1, m + 1) if p[j] != 0)
     return (torch.tensor([a for a, _ in pairs], dtype=torch.int64), torch.tensor([b for _, b in pairs], dtype=torch.int64))
+
+
+SEM_IGNORE, SEM_OUTSIDE = 255, 254
+
+
+def sem_rows_fwd(logits: torch.Tensor, coords: torch.Tensor, target: torch.Tensor, box: torch.Tensor, scale: int,
+                 weights: torch.Tensor):
+    """ps_rows_fwd in torch, in the dtype of `logits`: -> (label uint8 [N], ce [3] = (num / den, num, den), class_count int32 [C],
+    info int32 [4] = (rows inside the box, label indices outside the grid, labels in C..254, 0), err [C, N]).  `box` = int [6],
+    min_C then max_C, inclusive.  err_c = |[y == c] - p_c| for a row inside the box (1 - p_y as the sum of the other exponentials
+    over the sum), 0 outside; its fp32 bit pattern is the sort key."""
+    n, c = logits.shape
+    xyz = coords[:, 1:4].long()
+    lo, hi = box[:3].long(), box[3:].long()
+    inside = ((xyz >= lo) & (xyz <= hi)).all(dim=1)
+    idx = torch.div(xyz - lo, int(scale), rounding_mode="floor")
+    dims = torch.tensor(target.shape, dtype=torch.long)
+    in_grid = (idx < dims).all(dim=1) & inside
+    idx = idx.clamp(min=0).minimum(dims - 1)
+    raw = target[idx[:, 0], idx[:, 1], idx[:, 2]].long() if n else torch.zeros(0, dtype=torch.long)
+    bad_label = in_grid & (raw >= c) & (raw != SEM_IGNORE)
+    y = torch.where(in_grid & ~bad_label, raw, torch.full_like(raw, SEM_IGNORE))
+    y = torch.where(inside, y, torch.full_like(y, SEM_OUTSIDE))
+    m = logits.max(dim=1, keepdim=True).values if n else logits.new_zeros((0, 1))
+    e = torch.exp(logits - m)
+    fg = y[:, None] == torch.arange(c)[None, :]
+    total = e.sum(dim=1, keepdim=True)
+    others = torch.where(fg, torch.zeros_like(e), e).sum(dim=1, keepdim=True)
+    err = torch.where(fg, others / total, e / total)
+    err = torch.where(inside[:, None], err, torch.zeros_like(err)).t().contiguous()
+    known = y < c
+    w = weights.to(logits.dtype)[y.clamp(max=c - 1)]
+    nll = (torch.log(total[:, 0]) + m[:, 0]) - torch.gather(logits, 1, y.clamp(max=c - 1)[:, None])[:, 0]
+    zero = logits.new_zeros(())
+    num = torch.where(known, w * nll, zero).sum()
+    den = torch.where(known, w, zero).sum()
+    ce = torch.stack([num / den, num, den])
+    class_count = torch.bincount(y[known], minlength=c).to(torch.int32)
+    info = torch.tensor([int(inside.sum()), int((inside & ~in_grid).sum()), int(bad_label.sum()), 0], dtype=torch.int32)
+    return y.to(torch.uint8), ce, class_count, info, err
+
+
+def sem_sort_desc(keys: torch.Tensor) -> torch.Tensor:
+    """ps_sort_desc in torch: keys [S, M] (any ordered dtype) -> perm int32 [S, M], descending, equal keys in ascending index
+    order."""
+    return torch.sort(keys, dim=1, descending=True, stable=True).indices.to(torch.int32)
+
+
+def sem_lovasz_fwd(perm: torch.Tensor, label: torch.Tensor, err: torch.Tensor, class_count: torch.Tensor):
+    """ps_lovasz_fwd in torch, in the dtype of `err` [C, N]: -> (loss_c [C], coef [N, C], lovasz [1], present int32 [1]).  The
+    increments are the closed form in integers (include/pasco_semloss.h), formed in fp64 and rounded once."""
+    c, n = err.shape
+    p = perm.long()
+    lab = label.long()[p]                                   # [C, N] along the sorted order
+    cls = torch.arange(c)[:, None]
+    fg = lab == cls
+    inside = lab != SEM_OUTSIDE
+    g = class_count.long()[:, None]
+    cf = fg.long().cumsum(dim=1)                            # inclusive
+    i1 = inside.long().cumsum(dim=1)                        # i + 1 at a row inside the box
+    u = (g + i1 - cf).double()
+    inc = torch.where(fg, 1.0 / u, (g - cf).double() / ((u - 1.0) * u))
+    live = inside & (g > 0)
+    inc = torch.where(live, inc, torch.zeros_like(inc)).to(err.dtype)
+    loss_c = (torch.gather(err, 1, p) * inc).sum(dim=1)
+    coef_sorted = torch.where(fg, -inc, inc)
+    coef = torch.zeros((c, n), dtype=err.dtype).scatter_(1, p, coef_sorted).t().contiguous()
+    present = (class_count > 0).sum().to(torch.int32).reshape(1)
+    lovasz = (loss_c.sum() / present.clamp(min=1).to(err.dtype)).reshape(1)
+    return loss_c, coef, lovasz, present
+
+
+def sem_loss_bwd(logits: torch.Tensor, label: torch.Tensor, coef: torch.Tensor, weights: torch.Tensor, ce: torch.Tensor,
+                 present: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """ps_loss_bwd in torch: dlogits [N, C]; g [2] = the incoming gradients of (ce, lovasz).  A row labelled 254 is exactly 0."""
+    n, c = logits.shape
+    y = label.long()
+    p = torch.softmax(logits, dim=1)
+    known = y < c
+    onehot = y[:, None] == torch.arange(c)[None, :]
+    w = weights.to(logits.dtype)[y.clamp(max=c - 1)]
+    gc = torch.where(known, g[0] * w / ce[2], torch.zeros_like(w))
+    np_ = int(present)
+    gl = g[1] / np_ if np_ > 0 else torch.zeros_like(g[1])
+    d = gc[:, None] * (p - onehot.to(p.dtype)) + gl * p * (coef - (coef * p).sum(dim=1, keepdim=True))
+    return torch.where((y != SEM_OUTSIDE)[:, None], d, torch.zeros_like(d)) + 0.0
