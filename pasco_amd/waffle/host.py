@@ -167,6 +167,7 @@ def _search_one(xyz, start, order, g: SearchGrid, q, k: int, self_idx: int):
                         runs.append((start[row + xa], start[row + xa + 1]))
                     if xb <= gx - 1:
                         runs.append((start[row + xb], start[row + xb + 1]))
+        runs = [(max(int(a), 0), min(int(b), n)) for a, b in runs]             # clipped to [0, n), as the kernel clips them
         cand = [order[a:b] for a, b in runs if b > a]
         if not cand:
             continue
@@ -212,16 +213,32 @@ def knn_brute(xyz: np.ndarray, q: np.ndarray, k: int, exclude_self: bool) -> np.
 
 
 # ---- network pieces ---------------------------------------------------------------------------------------------------
-def flatten(tokens: np.ndarray, scale, shift, start, order, ncell: int) -> np.ndarray:
+def flatten_checked(tokens: np.ndarray, scale, shift, start, order, ncell: int):
+    """-> (grid fp32 [ncell, C], status).  A range of `start` that is reversed or leaves [0, n] is clipped and an entry of
+    `order` outside [0, n) is skipped (it is not counted either); both set STATUS_INDEX, as pw_flatten does."""
     n, C = tokens.shape
     t = tokens * scale[None].astype(_F) + shift[None].astype(_F)
-    cnt = (start[1:ncell + 1] - start[:ncell]).astype(np.int64)
+    a, b = start[:ncell].astype(np.int64), start[1:ncell + 1].astype(np.int64)
+    bad = bool(((a < 0) | (b > n) | (a > b)).any())
+    a, b = np.maximum(a, 0), np.minimum(b, n)
+    length = np.maximum(b - a, 0)
+    cnt = np.zeros(ncell, np.int64)
     total = np.zeros((ncell, C), np.float32)
-    for i in range(int(cnt.max()) if ncell else 0):
-        cells = np.nonzero(cnt > i)[0]
-        total[cells] = total[cells] + t[order[start[cells] + i]]
+    for i in range(int(length.max()) if ncell else 0):
+        cells = np.nonzero(length > i)[0]
+        p = order[a[cells] + i].astype(np.int64)
+        ok = (p >= 0) & (p < n)
+        bad |= not ok.all()
+        cells, p = cells[ok], p[ok]
+        total[cells] = total[cells] + t[p]
+        cnt[cells] += 1
     w = _F(1.0) / (cnt.astype(np.float32) + _F(1e-6))
-    return np.where(cnt[:, None] > 0, total * w[:, None], _F(0.0)).astype(np.float32)
+    grid = np.where(cnt[:, None] > 0, total * w[:, None], _F(0.0)).astype(np.float32)
+    return grid, (STATUS_INDEX if bad else 0)
+
+
+def flatten(tokens: np.ndarray, scale, shift, start, order, ncell: int) -> np.ndarray:
+    return flatten_checked(tokens, scale, shift, start, order, ncell)[0]
 
 
 def dwconv3x3(grid: np.ndarray, H: int, W: int, w: np.ndarray, bias: np.ndarray, relu: bool) -> np.ndarray:
@@ -240,20 +257,38 @@ def dwconv3x3(grid: np.ndarray, H: int, W: int, w: np.ndarray, bias: np.ndarray,
     return acc.reshape(grid.shape).astype(np.float32)
 
 
+def inflate_checked(tokens: np.ndarray, scale, grid: np.ndarray, cell):
+    """-> (out fp32 [n, C], status).  A cell outside [0, ncell) leaves out[p] = tokens[p] and sets STATUS_INDEX."""
+    c = np.asarray(cell).astype(np.int64)
+    ok = (c >= 0) & (c < grid.shape[0])
+    if grid.shape[0] == 0:
+        return tokens.copy(), (0 if ok.all() else STATUS_INDEX)
+    out = np.where(ok[:, None], tokens + scale[None].astype(_F) * grid[np.where(ok, c, 0)], tokens).astype(np.float32)
+    return out, (0 if ok.all() else STATUS_INDEX)
+
+
 def inflate(tokens: np.ndarray, scale, grid: np.ndarray, cell) -> np.ndarray:
-    return tokens + scale[None].astype(_F) * grid[cell]
+    return inflate_checked(tokens, scale, grid, cell)[0]
 
 
-def neigh_rows(feat: np.ndarray, knn_idx: np.ndarray, p0: int, np_: int, A: np.ndarray, b: np.ndarray) -> np.ndarray:
-    """-> fp32 [np * k, C]."""
+def neigh_rows_checked(feat: np.ndarray, knn_idx: np.ndarray, p0: int, np_: int, A: np.ndarray, b: np.ndarray):
+    """-> (fp32 [np * k, C], status).  A neighbour outside [0, n) counts as the point itself (every difference is 0) and sets
+    STATUS_INDEX."""
     k, F = knn_idx.shape[1], feat.shape[1]
-    nb = knn_idx[p0:p0 + np_].reshape(-1)
+    nb = knn_idx[p0:p0 + np_].reshape(-1).astype(np.int64)
     me = np.repeat(np.arange(p0, p0 + np_), k)
+    ok = (nb >= 0) & (nb < feat.shape[0])
+    nb = np.where(ok, nb, me)
     d = feat[nb] - feat[me]
     acc = np.broadcast_to(b[None].astype(_F), (nb.shape[0], A.shape[1])).copy()
     for f in range(F):
         acc = acc + A[f][None] * d[:, f:f + 1]
-    return np.where(acc > 0, acc, _F(0.0)).astype(np.float32)
+    return np.where(acc > 0, acc, _F(0.0)).astype(np.float32), (0 if ok.all() else STATUS_INDEX)
+
+
+def neigh_rows(feat: np.ndarray, knn_idx: np.ndarray, p0: int, np_: int, A: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """-> fp32 [np * k, C]."""
+    return neigh_rows_checked(feat, knn_idx, p0, np_, A, b)[0]
 
 
 def group_max(rows: np.ndarray, np_: int, k: int) -> np.ndarray:

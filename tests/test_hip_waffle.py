@@ -17,101 +17,15 @@ sys.path.insert(0, HERE)
 
 import waffle_cases as WC  # noqa: E402
 from pasco_amd.waffle import WaffleNet, host, prep  # noqa: E402
+from waffle_device import DEV, DeviceOps, dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-GUARD = 64
 
 
 @pytest.fixture(scope="module")
 def lib(hip):
     from pasco_amd.waffle.lib import waffle_lib
     return waffle_lib()
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-class DeviceOps:
-    """The pw_* entry points behind the methods of `waffle_cases.HostOps`: numpy in, numpy out.  Every output buffer has
-    GUARD entries behind it that must come back untouched, and every input must come back as it went up."""
-    name = "device"
-
-    def __init__(self, lib):
-        self.lib = lib
-
-    def _run(self, numel, dtype, fill, inputs, call, status=True):
-        out = torch.full((numel + GUARD,), fill, dtype=dtype, device=DEV)
-        st = torch.zeros(1 + GUARD, dtype=torch.int32, device=DEV)
-        ups = [dev(a) for a in inputs]
-        call(out, st[:1], *ups)
-        torch.cuda.synchronize(DEV)
-        assert bool((out[numel:] == fill).all()), "written past the end of the output"
-        assert not st[1:].any(), "written past the status word"
-        for t, a in zip(ups, inputs):
-            assert np.array_equal(t.cpu().numpy(), a), "an input was written"
-        res = out[:numel].cpu().numpy()
-        return (res, int(st[0].item())) if status else res
-
-    def voxel_keys(self, pc, mn, voxel):
-        n = pc.shape[0]
-        key, st = self._run(3 * n, torch.int32, -7, [pc, mn], lambda o, s, a, b: self.lib.voxel_keys(a, b, voxel, s, out=o))
-        return key.reshape(n, 3), st
-
-    def cell_index(self, pc, dims, lo, res, shape):
-        return self._run(pc.shape[0], torch.int32, -7, [pc], lambda o, s, a: self.lib.cell_index(a, dims, lo, res, shape, s, out=o))
-
-    def grid_cells(self, xyz, g):
-        return self._run(xyz.shape[0], torch.int32, -7, [xyz], lambda o, s, a: self.lib.grid_cells(a, g, s, out=o))
-
-    def cells_build(self, cell, ncell, order=None):
-        d_cell = dev(cell)
-        d_order = torch.sort(d_cell, stable=True)[1].to(torch.int32) if order is None else dev(order)
-        start, st = self._run(ncell + 1, torch.int32, -7, [cell], lambda o, s, a: self.lib.cells_build(a, ncell, s, start=o, order=d_order))
-        return start, d_order.cpu().numpy(), st
-
-    def knn(self, xyz, start, order, g, k):
-        n = xyz.shape[0]
-        return self._run(n * k, torch.int32, -7, [xyz, start, order], lambda o, s, a, b, c: self.lib.knn(a, b, c, g, k, out=o),
-                         status=False).reshape(n, k)
-
-    def nearest(self, xyz, start, order, g, q):
-        return self._run(q.shape[0], torch.int32, -7, [xyz, start, order, q],
-                         lambda o, s, a, b, c, d: self.lib.nearest(a, b, c, g, d, out=o), status=False)
-
-    def flatten(self, tokens, scale, shift, start, order, ncell):
-        C = tokens.shape[1]
-        grid, st = self._run(ncell * C, torch.float32, -3.0, [tokens, scale, shift, start, order],
-                             lambda o, s, a, b, c, d, e: self.lib.flatten(a, b, c, d, e, ncell, s, out=o))
-        return grid.reshape(ncell, C), st
-
-    def inflate(self, tokens, scale, grid, cell):
-        out, st = self._run(tokens.size, torch.float32, -3.0, [tokens, scale, grid, cell],
-                            lambda o, s, a, b, c, d: self.lib.inflate(a, b, c, d, s, out=o))
-        d_tok = dev(tokens)                                      # in place is allowed
-        self.lib.inflate(d_tok, dev(scale), dev(grid), dev(cell), torch.zeros(1, dtype=torch.int32, device=DEV), out=d_tok)
-        assert np.array_equal(d_tok.cpu().numpy().reshape(-1), out)
-        return out.reshape(tokens.shape), st
-
-    def dwconv3x3(self, g, H, W, w, b, relu):
-        return self._run(g.size, torch.float32, -3.0, [g, w, b], lambda o, s, a, ww, bb: self.lib.dwconv3x3(a, H, W, ww, bb, relu, out=o),
-                         status=False).reshape(g.shape)
-
-    def neigh_rows(self, feat, knn, p0, np_, A, b):
-        k, C = knn.shape[1], A.shape[1]
-        rows, st = self._run(np_ * k * C, torch.float32, -3.0, [feat, knn, A, b],
-                             lambda o, s, f, kk, a, bb: self.lib.neigh_rows(f, kk, p0, np_, a, bb, s, out=o))
-        assert st == 0
-        return rows.reshape(np_ * k, C)
-
-    def group_max(self, rows, np_, k, ld_out):
-        C = rows.shape[1]
-        wide = self._run(np_ * ld_out, torch.float32, -3.0, [rows],
-                         lambda o, s, r: self.lib.group_max(r, np_, k, o[:np_ * ld_out].view(np_, ld_out)[:, ld_out - C:]),
-                         status=False).reshape(np_, ld_out)
-        assert (wide[:, :ld_out - C] == -3.0).all(), "written outside the column slice"
-        return wide[:, ld_out - C:]
 
 
 @pytest.fixture(scope="module")
