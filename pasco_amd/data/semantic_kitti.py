@@ -1,7 +1,7 @@
 """SemanticKITTI / PaSCo on-disk formats -> the a0 input contract of the inference path.
 
-Restates, file format by file format, what the reference's data layer reads (no training-side label pyramids,
-no augmentation sampling - the caller passes the rigid transform T of each subnet):
+Restates, file format by file format, what the reference's data layer reads, and the training-side targets it builds from
+them (`build_train_item`; the caller passes the transform T of each subnet and the crop's draw - `data.augment` samples T):
 
   bit-packed voxel grids   pasco/data/semantic_kitti/io_data.py:11-24 (unpack), :35-45 (pack),
                            :114-138 (.bin occupancy, .label uint16, .invalid / .occluded)
@@ -12,6 +12,7 @@ no augmentation sampling - the caller passes the rigid transform T of each subne
   frame -> subnet item     kitti_dataset.py:339-455 (extent crop, radius, voxelise, transform) and :150-175
                            (min_C floored to the completion scale, max_C)
   items -> batch           pasco/data/semantic_kitti/collate.py:76-105 (global bounds rounded up to the scale)
+  training targets         kitti_dataset.py:142-288 (dense grids, multi-scale labels), :463-490 (crop), :594-664 (mask targets)
   rigid transforms         pasco/models/transform_utils.py:60-74 (`transform`), :123-161 (`transform_scene`)
 
 Pickles are Python pickles: load them only from sources you trust (the reference's own preprocessing output).
@@ -230,6 +231,143 @@ def collate(items: Sequence[Dict], complete_scale: int = 8) -> Dict:
             "input_pcd_instance_label": [it.get("input_pcd_instance_label") for it in items]}
 
 
+# ---- the training-side targets (host restatement; the device path is data/targets.py) ---------------------
+SCALES = (1, 2, 4)
+SEMANTIC_KITTI_THING_IDS = (1, 2, 3, 4, 5, 6, 7, 8)
+
+
+def crop_window_from_bounds(lo: torch.Tensor, hi: torch.Tensor, u) -> torch.Tensor:
+    """The training crop's window (kitti_dataset.py:463-471) from the bounds of the semantic samples -> fp64 [4] = (min x,
+    max x, min y, max y); a coordinate c is kept iff min <= c < max.  The dtypes are those of the reference's expression: the
+    0.8 extent and the slack are fp32 (an int32 tensor times a Python float), the product with `u` and everything after it
+    fp64.  `u`: three numbers in [0, 1); z is not cropped."""
+    lo, hi = lo.int(), hi.int()
+    size = (hi - lo) * 0.8
+    new_lo = lo + (hi - lo - size) * torch.as_tensor(np.asarray(u, dtype=np.float64).reshape(3))
+    new_hi = new_lo + size
+    return torch.stack([new_lo[0], new_hi[0], new_lo[1], new_hi[1]]).double()
+
+
+def crop_window(sem_coords: torch.Tensor, u) -> torch.Tensor:
+    return crop_window_from_bounds(sem_coords.min(dim=0)[0], sem_coords.max(dim=0)[0], u)
+
+
+def in_window(coords: torch.Tensor, window: torch.Tensor) -> torch.Tensor:
+    w = window.to(coords.device)
+    return (coords[:, 0] >= w[0]) & (coords[:, 0] < w[1]) & (coords[:, 1] >= w[2]) & (coords[:, 1] < w[3])
+
+
+def dense_labels(sem_sparse, sem_coords, ins_sparse, ins_coords, min_c, scene_size):
+    """The sparse samples written into grids of origin min_C (kitti_dataset.py:179-198): semantic filled with 255,
+    instance with 0."""
+    shape = [int(v) for v in scene_size]
+    sem = torch.full(shape, 255, dtype=torch.uint8)
+    c = (sem_coords - min_c).long()
+    sem[c[:, 0], c[:, 1], c[:, 2]] = sem_sparse.reshape(-1).to(torch.uint8)
+    ins = torch.zeros(shape, dtype=torch.uint8)
+    if ins_coords.shape[0] > 0:
+        c = (ins_coords - min_c).long()
+        ins[c[:, 0], c[:, 1], c[:, 2]] = ins_sparse.reshape(-1).to(torch.uint8)
+    return sem, ins
+
+
+def _blocks(grid: torch.Tensor, s: int) -> torch.Tensor:
+    X, Y, Z = grid.shape
+    return grid.reshape(X // s, s, Y // s, s, Z // s, s).permute(0, 2, 4, 1, 3, 5).reshape(X // s, Y // s, Z // s, s ** 3)
+
+
+def multiscale_labels(semantic_label: torch.Tensor, n_classes: int = 20):
+    """geo_labels / sem_labels at scales 1, 2, 4 (kitti_dataset.py:205-266) as integer rules over the s^3 blocks, equal to
+    the reference's one-hot poolings:
+      sem  the most frequent class of 1..n_classes-1 in the block (lowest index on a tie); without any, 0 if ALL voxels are
+           255, else 255 (sic: a block of empties, or of empties and unknowns, reads 255)
+      geo  255 if all voxels are 255, else 1 if any is in 1..254, else 0"""
+    sem = semantic_label
+    geo1 = torch.where(sem == 255, sem, (sem > 0).to(torch.uint8))
+    geo, lab = {"1_1": geo1}, {"1_1": sem}
+    for s in SCALES[1:]:
+        b = _blocks(sem, s)
+        counts = torch.stack([(b == c).sum(dim=-1) for c in range(1, n_classes)], dim=-1)
+        best = counts.argmax(dim=-1) + 1
+        any_class = counts.max(dim=-1)[0] > 0
+        all_unknown = (b == 255).all(dim=-1)
+        lab[f"1_{s}"] = torch.where(any_class, best, torch.where(all_unknown, 0, 255)).to(torch.uint8)
+        occupied = ((b > 0) & (b < 255)).any(dim=-1)
+        geo[f"1_{s}"] = torch.where(all_unknown, 255, occupied.long()).to(torch.uint8)
+    return geo, lab
+
+
+def mask_targets(semantic_label: torch.Tensor, instance_label: torch.Tensor, thing_ids=SEMANTIC_KITTI_THING_IDS):
+    """`prepare_mask_label` (kitti_dataset.py:594-664): the stuff classes present (ascending; not 0, not 255, not a thing),
+    then one entry per instance id present (ascending, not 0) whose class is the semantic label at the instance's first voxel
+    in row-major order.  -> {"labels": uint8 [T], "masks": bool [T, X, Y, Z]}.  Edge: a frame with no entry gives T = 0
+    (labels [0], masks [0, X, Y, Z]) where the reference's `torch.stack([])` raises."""
+    sem, ins = semantic_label, instance_label
+    labels, masks = [], []
+    for c in torch.unique(sem).tolist():
+        if c not in (0, 255) and c not in thing_ids:
+            labels.append(c)
+            masks.append(sem == c)
+    for i in torch.unique(ins).tolist():
+        if i != 0:
+            m = ins == i
+            labels.append(int(sem[m][0]))
+            masks.append(m)
+    if not masks:
+        return {"labels": torch.zeros(0, dtype=torch.uint8), "masks": torch.zeros((0,) + tuple(sem.shape), dtype=torch.bool)}
+    return {"labels": torch.tensor(labels, dtype=torch.uint8), "masks": torch.stack(masks)}
+
+
+def build_train_item(xyz: np.ndarray, vote: np.ndarray, intensity: np.ndarray, embedding: np.ndarray,
+                     semantic_label: np.ndarray, instance_label: np.ndarray, T: Optional[torch.Tensor] = None,
+                     complete_scale: int = 8, point_labels: Optional[np.ndarray] = None, *, crop_u=None,
+                     thing_ids=SEMANTIC_KITTI_THING_IDS, n_classes: int = 20, frame_id: Optional[str] = None,
+                     sequence: Optional[str] = None) -> Dict:
+    """The whole of `KittiDataset.get_individual` (kitti_dataset.py:142-288) for one subnet, on the host: `build_item` plus
+    the training crop (`crop_u` = the three numbers in [0, 1) the reference draws with np.random.rand(3); None = no crop,
+    the reference's split="val"), the bounds of what the crop keeps, the dense label grids, the multi-scale labels and the
+    mask targets.  Returns the reference's keys."""
+    it = build_item(xyz, vote, intensity, embedding, semantic_label, instance_label, T, complete_scale, point_labels)
+    sem_f, sem_c = it["semantic_label_sparse"]
+    ins_f, ins_c = it["instance_label_sparse"]
+    in_feat, in_coord, plab = it["in_feat"], it["in_coord"], it["input_pcd_instance_label"]
+    if crop_u is not None:
+        w = crop_window(sem_c, crop_u)
+        keep_in, keep_sem, keep_ins = in_window(in_coord, w), in_window(sem_c, w), in_window(ins_c, w)
+        in_feat, in_coord = in_feat[keep_in], in_coord[keep_in]
+        sem_f, sem_c, ins_f, ins_c = sem_f[keep_sem], sem_c[keep_sem], ins_f[keep_ins], ins_c[keep_ins]
+    min_c, max_c = sem_c.min(dim=0)[0], sem_c.max(dim=0)[0]
+    if ins_c.shape[0] > 0:
+        min_c = torch.min(min_c, ins_c.min(dim=0)[0])
+        max_c = torch.max(max_c, ins_c.max(dim=0)[0])
+    min_c, max_c = completion_bounds(min_c, max_c, complete_scale)
+    scene = compute_scene_size(min_c, max_c, scale=complete_scale)
+    sem, ins = dense_labels(sem_f, sem_c, ins_f, ins_c, min_c, scene)
+    geo, lab = multiscale_labels(sem, n_classes)
+    sem_o, ins_o = torch.from_numpy(semantic_label).to(torch.uint8), torch.from_numpy(instance_label).to(torch.uint8)
+    return {"xyz": it["xyz"], "frame_id": frame_id, "sequence": sequence, "in_feat": in_feat, "in_coord": in_coord,
+            "T": it["T"], "min_C": min_c, "max_C": max_c, "semantic_label": sem, "instance_label": ins,
+            "mask_label": mask_targets(sem, ins, thing_ids), "geo_labels": geo, "sem_labels": lab,
+            "semantic_label_origin": sem_o, "instance_label_origin": ins_o,
+            "mask_label_origin": mask_targets(sem_o, ins_o, thing_ids), "input_pcd_instance_label": plab}
+
+
+def collate_train(items: Sequence[Dict], complete_scale: int = 8) -> Dict:
+    """Training items -> the reference's training batch (collate.py:11-107): `collate`'s keys plus the per-subnet label
+    lists, geo_labels / sem_labels as dicts of lists, and the stacked origin grids."""
+    out = collate(items, complete_scale)
+    out.update({"frame_id": [it["frame_id"] for it in items], "sequence": [it["sequence"] for it in items],
+                "geo_labels": {f"1_{s}": [it["geo_labels"][f"1_{s}"] for it in items] for s in SCALES},
+                "sem_labels": {f"1_{s}": [it["sem_labels"][f"1_{s}"] for it in items] for s in SCALES},
+                "semantic_label": [it["semantic_label"] for it in items],
+                "instance_label": [it["instance_label"] for it in items],
+                "semantic_label_origin": torch.stack([it["semantic_label_origin"] for it in items]),
+                "instance_label_origin": torch.stack([it["instance_label_origin"] for it in items]),
+                "mask_label": [it["mask_label"] for it in items],
+                "mask_label_origin": [it["mask_label_origin"] for it in items]})
+    return out
+
+
 class FrameReader:
     """Directory layout of the reference's SemanticKITTI setup (kitti_dataset.py:100-112,344-370):
         <root>/dataset/sequences/<seq>/labels/<frame>.label
@@ -295,6 +433,33 @@ class FrameReader:
         plab = read_point_instance_labels(pts) if os.path.exists(pts) else None
         items = [build_item(xyz, vote, intensity, emb, sem, ins, T, self.complete_scale, plab) for T in Ts]
         return collate(items, self.complete_scale)
+
+    def train_batch(self, sequence: str, frame_id: str, Ts: Sequence[torch.Tensor], crop_u=None, embedding_index: int = 0,
+                    device=None, n_classes: int = 20) -> Dict:
+        """The batch `Net.step` consumes: `batch`'s keys plus the label targets of every subnet under its transform (`Ts`, e.g.
+        from `data.augment.random_transformation`) and its training crop (`crop_u`: len(Ts) x 3 numbers in [0, 1), what the
+        reference draws with np.random.rand(3) per item; None = no crop, the reference's validation items).  `device=None` (or
+        a CPU device) runs the host restatement `build_train_item`; a GPU device runs the pf_* kernels for the points and the
+        pt_* kernels for the targets (`data.targets`), bit-equal, with the tensors left on that device."""
+        _, feats, pts = self.paths(sequence, frame_id)
+        if self.features is not None:
+            scan = read_pointcloud(os.path.join(self.root, "dataset", "sequences", sequence, "velodyne", f"{frame_id}.bin"))
+            feats = self.features.frame(scan, int(frame_id))
+        sem, ins = self.labels(sequence, frame_id)
+        us = None if crop_u is None else np.asarray(crop_u, dtype=np.float64).reshape(len(Ts), 3)
+        plab = read_point_instance_labels(pts) if os.path.exists(pts) else None
+        if device is not None and torch.device(device).type == "cuda":
+            from . import device_prep as DP
+            from .targets import assemble_train_batch
+            base = prepare_semantic_kitti_on_device(feats, sem, ins, Ts, device, embedding_index, self.complete_scale, plab)
+            return assemble_train_batch(base, DP.upload(sem, device), DP.upload(ins, device), thing_ids=self.thing_ids,
+                                        n_classes=n_classes, complete_scale=self.complete_scale, crop_u=us, frame_id=frame_id,
+                                        sequence=sequence)
+        xyz, vote, intensity, emb = read_waffleiron_features(feats, embedding_index=embedding_index)
+        items = [build_train_item(xyz, vote, intensity, emb, sem, ins, T, self.complete_scale, plab,
+                                  crop_u=None if us is None else us[m], thing_ids=self.thing_ids, n_classes=n_classes,
+                                  frame_id=frame_id, sequence=sequence) for m, T in enumerate(Ts)]
+        return collate_train(items, self.complete_scale)
 
 
 def prepare_semantic_kitti_on_device(feats_path: str, semantic_label: np.ndarray, instance_label: np.ndarray,

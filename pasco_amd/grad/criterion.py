@@ -207,9 +207,11 @@ class SetCriterion(nn.Module):
             ci = voxel_logits.coordinates_at(i)
             coords = torch.cat([torch.zeros_like(ci[:, :1]), ci], dim=1)
         origin = (0, 0, 0) if min_C is None else [int(v) for v in torch.as_tensor(min_C).reshape(3).tolist()]
-        masks = targets[i]["masks"].to(coords.device)
         unknown = None if unknown_mask_dense is None else unknown_mask_dense[0].to(coords.device)
-        packed = pack_targets(masks, unknown, coords, origin)
+        if hasattr(targets[i], "pack"):       # data.targets.TargetMasks: the words straight from the label grids, no [T, X, Y, Z]
+            packed = targets[i].pack(coords, unknown, origin)
+        else:
+            packed = pack_targets(targets[i]["masks"].to(coords.device), unknown, coords, origin)
         cache[key] = (c_all, packed)
         return packed
 
