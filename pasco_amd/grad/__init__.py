@@ -1,7 +1,8 @@
 """Training operators of the sparse convolution family (include/pasco_grad.h): the inverse of a neighbour table, the weight
 gradient and the bias gradient; of the dense <-> rows operators and local max pooling (include/pasco_rowgrad.h); and of the
 masked cross-attention (include/pasco_attngrad.h); the matcher and mask losses (include/pasco_match.h); and the semantic
-completion losses (include/pasco_semloss.h).  `host` restates them in torch (CPU tensors, the tensor's dtype), `lib` binds the
+completion losses (include/pasco_semloss.h); and of training-mode batch normalisation over rows, local or synchronised
+(include/pasco_norm.h: `normlib` binds the `pn_*` entry points, `norm.batch_norm_rows` is the operator).  `host` restates them in torch (CPU tensors, the tensor's dtype), `lib` binds the
 `pg_*` entry points, `rowlib` the `pr_*` ones, `attnlib` the `pa_*` ones, `matchlib` the `pm_*` ones and `semlib` the `ps_*` ones;
 the functions here serve a tensor from the one its device calls for.  The autograd functions that use them are
 `pasco_amd.me.autograd`, `pasco_amd.grad.attention`, `pasco_amd.grad.criterion` and `pasco_amd.grad.semloss`."""
@@ -91,3 +92,4 @@ def mask_loss_bwd(logits, tbits, flags, tgt_of_query, coef, t: int):
 
 from .semloss import (SemComplLossFunction, compute_sem_compl_loss, compute_sem_compl_loss_kitti360,  # noqa: E402,F401
                       sem_compl_loss)
+from .norm import BatchNormRowsFunction, batch_norm_rows, group_gather  # noqa: E402,F401

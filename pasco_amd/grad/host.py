@@ -1,4 +1,4 @@
-"""Torch restatement of include/pasco_grad.h, include/pasco_rowgrad.h and include/pasco_attngrad.h for CPU tensors: index
+"""Torch restatement of include/pasco_grad.h, include/pasco_rowgrad.h, include/pasco_attngrad.h and include/pasco_norm.h for CPU tensors: index
 operations and matrix products in the tensor's dtype.  The
 CPU tests run on it and `pasco_amd.me.autograd` uses it where the features are not on a GPU.  Same results as the kernels up to
 the order of the fp32 sums."""
@@ -356,3 +356,106 @@ def sem_loss_bwd(logits: torch.Tensor, label: torch.Tensor, coef: torch.Tensor, 
     gl = g[1] / np_ if np_ > 0 else torch.zeros_like(g[1])
     d = gc[:, None] * (p - onehot.to(p.dtype)) + gl * p * (coef - (coef * p).sum(dim=1, keepdim=True))
     return torch.where((y != SEM_OUTSIDE)[:, None], d, torch.zeros_like(d)) + 0.0
+
+
+# ---- include/pasco_norm.h ---------------------------------------------------------------------------------------------------
+NORM_TILE_ROWS = 128            # PN_TILE_ROWS
+ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
+
+
+def norm_moments_merge(recs: torch.Tensor) -> torch.Tensor:
+    """pn_moments_merge in torch: recs fp64 [r, 3, c] -> [3, c], the pairwise update in ascending r from (0, 0, 0); a record of
+    count 0 is skipped (the first record with rows comes out as it is: w = 1, n = 0)."""
+    r, _, c = recs.shape
+    n = torch.zeros(c, dtype=torch.float64, device=recs.device)
+    mean, m2 = n.clone(), n.clone()
+    for i in range(r):
+        nb, mb, qb = recs[i, 0], recs[i, 1], recs[i, 2]
+        has = nb > 0
+        tot = n + torch.where(has, nb, torch.zeros_like(nb))
+        w = torch.where(has, nb / torch.where(has, tot, torch.ones_like(tot)), torch.zeros_like(nb))
+        d = mb - mean
+        mean, m2, n = torch.where(has, mean + d * w, mean), torch.where(has, (m2 + qb) + (d * d) * (n * w), m2), tot
+    return torch.stack([n, mean, m2])
+
+
+def norm_moments(x: torch.Tensor) -> torch.Tensor:
+    """pn_moments in torch: x [n, c] -> fp64 [3, c]; one record per NORM_TILE_ROWS rows, M2 about the tile's own mean, merged in
+    ascending tile order."""
+    n, c = x.shape
+    recs = []
+    for r0 in range(0, n, NORM_TILE_ROWS):
+        t = x[r0:r0 + NORM_TILE_ROWS].double()
+        mean = t.sum(dim=0) / t.shape[0]
+        recs.append(torch.stack([torch.full_like(mean, t.shape[0]), mean, (t - mean).square().sum(dim=0)]))
+    return norm_moments_merge(torch.stack(recs) if recs else torch.zeros((0, 3, c), dtype=torch.float64, device=x.device))
+
+
+def norm_finish(rec: torch.Tensor, eps: float, momentum: float, running_mean, running_var, dtype=torch.float32) -> torch.Tensor:
+    """pn_finish in torch: rec fp64 [3, c] -> mean_rstd [2, c] in `dtype`; the running statistics move in place where count > 0."""
+    n, mean, m2 = rec[0], rec[1], rec[2]
+    has = n > 0
+    var = torch.where(has, m2 / torch.where(has, n, torch.ones_like(n)), torch.zeros_like(m2))
+    out = torch.stack([torch.where(has, mean, torch.zeros_like(mean)), 1.0 / torch.sqrt(var + eps)]).to(dtype)
+    with torch.no_grad():
+        if running_mean is not None:
+            new = (1.0 - momentum) * running_mean.double() + momentum * mean
+            running_mean.copy_(torch.where(has, new, running_mean.double()).to(running_mean.dtype))
+        if running_var is not None:
+            new = (1.0 - momentum) * running_var.double() + momentum * (m2 / torch.where(n > 1, n - 1, torch.ones_like(n)))
+            running_var.copy_(torch.where(has, new, running_var.double()).to(running_var.dtype))
+    return out
+
+
+def _norm_z(x, mean_rstd, weight, bias):
+    xh = (x - mean_rstd[0]) * mean_rstd[1]
+    z = xh if weight is None else xh * weight
+    return xh, (z if bias is None else z + bias)
+
+
+def _norm_act_grad(z, act: int, slope: float):
+    if act == ACT_RELU:
+        return (z > 0).to(z.dtype)
+    if act == ACT_LEAKY:
+        return torch.where(z > 0, torch.ones_like(z), torch.full_like(z, slope))
+    return torch.ones_like(z)
+
+
+def norm_apply(x, mean_rstd, weight, bias, act: int, slope: float) -> torch.Tensor:
+    """pn_apply in torch, in the dtype of `x`."""
+    _, z = _norm_z(x, mean_rstd, weight, bias)
+    if act == ACT_RELU:
+        return torch.where(z > 0, z, torch.zeros_like(z))
+    if act == ACT_LEAKY:
+        return torch.where(z > 0, z, slope * z)
+    return z
+
+
+def norm_sums_merge(sums: torch.Tensor) -> torch.Tensor:
+    """pn_sums_merge in torch: fp64 [r, 2, c] -> [2, c], added in ascending r."""
+    out = torch.zeros(sums.shape[1:], dtype=torch.float64, device=sums.device)
+    for i in range(sums.shape[0]):
+        out = out + sums[i]
+    return out
+
+
+def norm_bwd_sums(dy, x, mean_rstd, weight, bias, act: int, slope: float) -> torch.Tensor:
+    """pn_bwd_sums in torch: -> fp64 [2, c] = (sum g, sum g * xhat), per-tile partials added in ascending tile order."""
+    n, c = x.shape
+    xh, z = _norm_z(x, mean_rstd, weight, bias)
+    g = dy * _norm_act_grad(z, act, slope)
+    parts = [torch.stack([g[r0:r0 + NORM_TILE_ROWS].double().sum(dim=0),
+                          (g[r0:r0 + NORM_TILE_ROWS].double() * xh[r0:r0 + NORM_TILE_ROWS].double()).sum(dim=0)])
+             for r0 in range(0, n, NORM_TILE_ROWS)]
+    return norm_sums_merge(torch.stack(parts) if parts else torch.zeros((0, 2, c), dtype=torch.float64, device=x.device))
+
+
+def norm_bwd_dx(dy, x, mean_rstd, weight, bias, act: int, slope: float, total_sums, total_rec) -> torch.Tensor:
+    """pn_bwd_dx in torch, in the dtype of `x`: weight * rstd * (g - S0 / N - xhat * S1 / N), N from `total_rec`."""
+    xh, z = _norm_z(x, mean_rstd, weight, bias)
+    g = dy * _norm_act_grad(z, act, slope)
+    cnt = total_rec[0]
+    inv = torch.where(cnt > 0, 1.0 / torch.where(cnt > 0, cnt, torch.ones_like(cnt)), torch.zeros_like(cnt))
+    a0, a1 = (total_sums[0] * inv).to(x.dtype), (total_sums[1] * inv).to(x.dtype)
+    ws = mean_rstd[1] if weight is None else weight * mean_rstd[1]
+    return ws * ((g - a0) - xh * a1)

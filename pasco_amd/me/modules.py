@@ -39,6 +39,19 @@ def set_me_conv(mode: str) -> None:
     _ME_CONV = mode
 
 
+_ME_NORM = os.environ.get("PASCO_ME_NORM", "torch")
+assert _ME_NORM in ("torch", "device"), f"PASCO_ME_NORM={_ME_NORM!r}: 'torch' or 'device'"
+
+
+def set_me_norm(mode: str) -> None:
+    """"torch" (default): a training-mode `MinkowskiBatchNorm` is torch's batch_norm; "device": on fp32 GPU rows it is
+    `pasco_amd.grad.norm.batch_norm_rows` (the pn_* kernels: fixed-order statistics).  `MinkowskiSyncBatchNorm`
+    in a process group of more than one rank takes the pn_* route under either setting."""
+    global _ME_NORM
+    assert mode in ("torch", "device")
+    _ME_NORM = mode
+
+
 class _ConvBase(MinkowskiModuleBase):
     is_transpose = False
 
@@ -230,19 +243,46 @@ class MinkowskiBatchNorm(nn.Module):
         if m.training:                     # the running statistics move: no fold made before this call stands for them
             self.__dict__.pop("_ph_me_folded", None)
             m.__dict__.pop("_ph_folded", None)
+            use, gather = self._rows_route(x.F)
+            if use:
+                from ..grad.norm import batch_norm_rows
+                return _same_map(x, batch_norm_rows(x.F, m.weight, m.bias, m.running_mean, m.running_var, m.num_batches_tracked,
+                                                    m.momentum, m.eps, gather=gather))
         return _same_map(x, self.bn(x.F))
+
+    def _rows_route(self, feats: torch.Tensor):
+        """-> (a training-mode forward goes through `batch_norm_rows`, its `gather`)."""
+        return _ME_NORM == "device" and feats.is_cuda and feats.dtype == torch.float32, None
 
 
 class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
-    """Inference engine: statistics are frozen, so the synchronised variant is plain BatchNorm1d with
-    the same state-dict keys (reference: unet3d_sparse_v2.py:172-175)."""
+    """Batch normalisation whose training-mode mean and variance are taken over the rows of ALL ranks of `process_group`
+    (reference: unet3d_sparse_v2.py:172-175 converts the whole encoder and decoder and trains with one scene per GPU).  Same
+    state-dict keys as `MinkowskiBatchNorm`.
+
+    In training mode, with torch.distributed initialised and more than one rank in the group (torch.nn.SyncBatchNorm's own
+    condition), the forward is `pasco_amd.grad.norm.batch_norm_rows` with `group_gather(process_group)`: one all-gather of the
+    moments record per forward, one of the gradient sums per backward, the same statistics bit for bit on every rank.  EVERY
+    rank has to call the module (a rank without rows passes its `[0, c]` tensor).  Otherwise - eval mode, no process group, one
+    rank - it is `MinkowskiBatchNorm`."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, process_group=None):
+        super().__init__(num_features, eps, momentum, affine, track_running_stats)
+        self.process_group = process_group
+
+    def _rows_route(self, feats: torch.Tensor):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.process_group) > 1:
+            from ..grad.norm import group_gather
+            return True, group_gather(self.process_group)
+        return super()._rows_route(feats)
 
     @classmethod
     def convert_sync_batchnorm(cls, module, process_group=None):
         out = module
         if isinstance(module, MinkowskiBatchNorm) and not isinstance(module, MinkowskiSyncBatchNorm):
             out = cls(module.bn.num_features, module.bn.eps, module.bn.momentum, module.bn.affine,
-                      module.bn.track_running_stats)
+                      module.bn.track_running_stats, process_group)
             out.bn.load_state_dict(module.bn.state_dict())
             out.train(module.training)
         for name, child in module.named_children():
