@@ -50,18 +50,7 @@ extern "C" int ph_dma_trace_read(unsigned long long *host_out) {
 constexpr int DMA_DENSE_KVOL = 100;
 constexpr int DMA_KMAX = 32;   // kernel offsets one workgroup walks (its slice of the split over the offsets)
 
-#ifdef PH_DEV
-// Development build only: bit 8 of the mask selects the 256-row / 8-wave tiles (measured no faster: one workgroup per CU convoys).
-// The phase-ablation bits of round 2 (skip MFMAs / gathers / fragment reads; profiles/r2c - r2e) are gone from the kernel:
-// their runtime branches cost ~3 % in the loop.
-static int g_dma_ablate = 0;
-static int g_dma_tall = 0;
-int ph_dma_ablate_bits() { return g_dma_ablate; }
-extern "C" void ph_conv_dma_set_ablate(int mask) { g_dma_ablate = mask & 0xff; g_dma_tall = (mask & 0x100) ? 1 : 0; }
-#else
-constexpr int g_dma_ablate = 0, g_dma_tall = 0;     // the product library has no experiment state
-int ph_dma_ablate_bits() { return 0; }
-#endif
+static_assert(DMA_KMAX == CONV_DMA_KMAX && DMA_DENSE_KVOL == CONV_DMA_DENSE_KVOL, "the planner (conv_plan.h) sizes the slices for this index table");
 
 // One workgroup = WAVES (4 or 8) waves as WM x WN, tile BM = WM*TM*32 rows (128 / 256) x BN = WN*TN*32 channels,
 // 32 input channels per stage.  Everything that crosses the vector-memory path (gathered rows AND the weight tile of
@@ -153,7 +142,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) k_conv_dma(ConvArgsH a) {
     // (beyond the grid's faces: the bottleneck orders its sites z-major so that a 128-row tile lies in ONE z plane, and
     // 30 % of the (tile, offset) stages of the (7, 7, 5) kernels are then empty) are dropped from the stage
     // list: the walk goes over kmap[0 .. nvalid).  Empty stages add exact zeros, so the sums do not change -----------------
-    // the list lives in the LAST offset slot of the index table (such launches walk at most DMA_KMAX - 1 offsets, ph_conv_dma_try:
+    // the list lives in the LAST offset slot of the index table (such launches walk at most DMA_KMAX - 1 offsets, conv_plan.h:
     // the tile's 80 KB of LDS are what lets two workgroups share a CU - not one byte more)
     static_assert(BM >= 2 * DMA_KMAX + 4, "the stage list fits one offset slot of the index table");
     int *kmap = idx_lds + (DMA_KMAX - 1) * BM;         // [DMA_KMAX] valid offset slots, then [DMA_KMAX] flags, then the count
@@ -433,31 +422,20 @@ __global__ void __launch_bounds__(WAVES * 64, 2) k_conv_dma(ConvArgsH a) {
   DMA_STAMP(4);
 }
 
-template <int WAVES, int WM, int WN, int TM, int TN>
-static int launch_dma(const ConvArgsH &a, hipStream_t st) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  ConvArgsH args = a;
-  args.n_row_tiles = (int)((a.n_out + BM - 1) / BM);
-  args.n_col_tiles = (a.cout + BN - 1) / BN;
-  const int ntiles = args.n_row_tiles * args.n_col_tiles;
-  const int grid = ((ntiles + 7) / 8) * 8;
-  const bool emit = args.out_split != nullptr && args.ksplit == 1;
-  static const bool inter = [] { const char *e = PH_DEV_ENV("PASCO_CONV_DMA_INTER"); return e == nullptr || atoi(e) != 0; }();
-  if (inter && WAVES == 4) {     // default: DMA instructions between the MFMAs (5-10 % on every layer; =0: in front of them)
-    if (emit)
-      hipLaunchKernelGGL((k_conv_dma<WAVES, WM, WN, TM, TN, true, true>), dim3(grid, 1), dim3(WAVES * 64), 0, st, args);
-    else
-      hipLaunchKernelGGL((k_conv_dma<WAVES, WM, WN, TM, TN, false, true>), dim3(grid, args.ksplit), dim3(WAVES * 64), 0, st, args);
-  } else if (emit)
-    hipLaunchKernelGGL((k_conv_dma<WAVES, WM, WN, TM, TN, true>), dim3(grid, 1), dim3(WAVES * 64), 0, st, args);
-  else
-    hipLaunchKernelGGL((k_conv_dma<WAVES, WM, WN, TM, TN, false>), dim3(grid, args.ksplit), dim3(WAVES * 64), 0, st, args);
-  PH_LAUNCH_CHECK();
-  if (args.ksplit > 1) {
-    if (int rc = ph_launch_splitk_epilogue(args, st)) return rc;
-  }
-  ph_record_cfg(2, BM, BN, 32, args.ksplit, emit ? 1 : 0, 4, WAVES);
-  return 0;
+// The template switch: tile shape from the step (128 x 32 / 64 / 128 on 4 waves; the development build's 256-row tiles on 8), EMIT,
+// and INTER = DMA instructions between the MFMAs (the default on 4 waves: 5-10 % on every layer) or in front of them.
+int ph_conv_dma_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st) {
+  ConvKernelFn k;
+#define DMA_CASE(W, WM, WN, TM, TN)                                                                                      \
+  k = s.inter ? (s.emit ? k_conv_dma<W, WM, WN, TM, TN, true, true> : k_conv_dma<W, WM, WN, TM, TN, false, true>)        \
+              : (s.emit ? k_conv_dma<W, WM, WN, TM, TN, true> : k_conv_dma<W, WM, WN, TM, TN, false>)
+  if (s.bn == 32) DMA_CASE(4, 4, 1, 1, 1);
+  else if (s.bn == 64 && s.waves == 8) DMA_CASE(8, 8, 1, 1, 2);
+  else if (s.bn == 64) DMA_CASE(4, 4, 1, 1, 2);
+  else if (s.waves == 8) DMA_CASE(8, 4, 2, 2, 2);
+  else DMA_CASE(4, 2, 2, 2, 2);
+#undef DMA_CASE
+  return ph_launch_tiles(k, a, s, st);
 }
 
 // 256 zero bytes per device for rows without a neighbour: the one piece of device memory the library owns
@@ -475,67 +453,6 @@ const char *ph_dma_zero_line() {
     zero[dev] = (const char *)p;
   }
   return zero[dev];
-}
-
-// scratch the caller offered for splits over the kernel offsets (ph_conv_desc.splitk_ws), carried in the argument block
-static inline void *g_tail_ws(const ConvArgsH &a) { return a.tail_ws; }
-static inline int64_t g_tail_ws_bytes(const ConvArgsH &a) { return a.tail_ws_bytes; }
-
-// Takes the launch when the shape fits the DMA pipeline; returns -1 when the caller should use k_conv_h2.
-// `a` arrives fully prepared (tile-independent fields, ksplit / partial chosen by the caller for 128-row tiles).
-int ph_conv_dma_try(const ConvArgsH &a_in, int bn, hipStream_t st) {
-  const int kper = (a_in.kvol + a_in.ksplit - 1) / a_in.ksplit;
-  if (kper > DMA_KMAX - (a_in.kvol > DMA_DENSE_KVOL ? 1 : 0)) return -1;     // dense GEMMs: the last index slot holds the stage list
-  const char *zero = ph_dma_zero_line();
-  if (zero == nullptr) return -1;
-  ConvArgsH a = a_in;
-  a.zero = zero;
-  a.ablate = g_dma_ablate & 0x85;      // experiment switches (tools/layer_ab.py): bit 0 = the long pipeline for short launches too,
-                                    // bit 2 = no dropping of empty (tile, offset) stages in the dense implicit GEMMs
-  // timing experiments (wrong results by design): 0x10 drops the per-axis table residual, 0x40 the dense residual
-  if (g_dma_ablate & 0x10) a.axis_table = nullptr;
-  if (g_dma_ablate & 0x40) a.residual = nullptr;
-  // 256-row tiles (8 waves, one workgroup per CU) when they still cover every CU about twice; else 128-row tiles
-  const int64_t ncol = (a.cout + bn - 1) / bn;
-  const bool tall = bn >= 64 && ((a.n_out + 255) / 256) * ncol * a.ksplit >= 2 * 256 && g_dma_tall;
-  if (bn == 32) return launch_dma<4, 4, 1, 1, 1>(a, st);
-  if (bn == 64) return tall ? launch_dma<8, 8, 1, 1, 2>(a, st) : launch_dma<4, 4, 1, 1, 2>(a, st);
-  if (tall) return launch_dma<8, 4, 2, 2, 2>(a, st);
-  // ---- tail split (128-wide tiles, two workgroups per CU = 512 resident tiles): every tile of a launch does the same work
-  // (all kvol offsets, whatever the map's sparsity), so a launch of T tiles runs in ceil(T / 512) rounds and a small last
-  // round leaves most of the chip idle for a whole tile time (559 tiles: 2 rounds for 1.09 rounds of work).  When fewer than
-  // half a round of row tiles is left over, they go into a second launch that is split over the kernel offsets so that it
-  // fills the chip with short workgroups; only those rows pay the partial-sum reduction. ----------------------------------
-  static const bool tail_on = [] { const char *e = PH_DEV_ENV("PASCO_CONV_TAIL"); return e == nullptr || atoi(e) != 0; }();
-  const int64_t trow = (a.n_out + 127) / 128;
-  const int64_t slots = 512 / ncol;               // row tiles of one full round
-  const int64_t rounds = trow / slots, rest = trow - rounds * slots;
-  if (tail_on && a.ksplit == 1 && a.tile_k == nullptr && a.nbr != nullptr && a.kvol >= 8 && !a.win_gather && rounds >= 1 &&
-      rest > 0 && 2 * rest <= slots && a_in.partial == nullptr && g_tail_ws(a_in) != nullptr) {
-    int ks = (int)(slots / rest);
-    if (ks > a.kvol / 3) ks = a.kvol / 3;
-    if (ks > 16) ks = 16;
-    // no empty slices: the kernel gives every slice ceil(kvol / ks) offsets, so e.g. 27 offsets in 8 slices of 4 leaves the
-    // eighth with nothing - its workgroups would only write (and the reduction read) zeros
-    while (ks > 1 && (a.kvol + (a.kvol + ks - 1) / ks - 1) / ((a.kvol + ks - 1) / ks) != ks) --ks;
-    const int64_t r0 = (trow - rest) * 128, tail_rows = a.n_out - r0;
-    if (ks >= 2 && (int64_t)ks * tail_rows * a.cout * 4 <= g_tail_ws_bytes(a_in)) {
-      ConvArgsH head = a;
-      head.n_out = r0;
-      if (int rc = launch_dma<4, 2, 2, 2, 2>(head, st)) return rc;
-      ConvArgsH tail = a;
-      tail.n_out = tail_rows;
-      tail.nbr = a.nbr + r0;
-      if (tail.out) tail.out = a.out + r0 * a.cout;
-      if (tail.out_split) tail.out_split = a.out_split + r0 * a.cout * 2;
-      if (tail.residual) tail.residual = a.residual + r0 * a.cout;
-      if (tail.axis_coords) tail.axis_coords = a.axis_coords + r0 * 4;
-      tail.ksplit = ks;
-      tail.partial = (float *)g_tail_ws(a_in);
-      return launch_dma<4, 2, 2, 2, 2>(tail, st);     // records its configuration: the launch reads as "ksplit"
-    }
-  }
-  return launch_dma<4, 2, 2, 2, 2>(a, st);
 }
 
 #ifdef PH_DEV

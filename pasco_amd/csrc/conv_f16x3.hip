@@ -493,7 +493,7 @@ extern "C" int ph_split_rows(const float *in, int64_t n, int32_t c, const float 
   PH_REQUIRE((((uintptr_t)in | (uintptr_t)out_split) & 15) == 0, "split_rows: 16-byte alignment");
   const int cpad = (c + 31) / 32 * 32;
   const int64_t total = n * (cpad / 8);
-  const float neg = pro_act == PH_ACT_RELU ? 0.f : (pro_act == PH_ACT_LEAKY ? slope : 1.f);
+  const float neg = neg_of(pro_act, slope);
   const int has_pro = (pro_scale || pro_shift || pro_act != PH_ACT_NONE) ? 1 : 0;
   hipLaunchKernelGGL(k_split_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ph_stream(stream), in, n, c, cpad,
                      pro_scale, pro_shift, has_pro, neg, ldexpf(1.f, exp2), (_Float16 *)out_split, status);
@@ -549,132 +549,96 @@ __global__ void __launch_bounds__(256) k_splitk_epilogue(ConvArgsH a) {
   }
 }
 
-int ph_launch_splitk_epilogue(const ConvArgsH &args, hipStream_t st) {
+// reduction + epilogue of a split over the kernel offsets (after a launch with args.ksplit > 1)
+static int ph_launch_splitk_epilogue(const ConvArgsH &args, hipStream_t st) {
   const int64_t total = args.n_out * args.cout;
   hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, args);
   PH_LAUNCH_CHECK();
   return 0;
 }
 
-template <int BM, int KC, int WM, int WN, int TM, int TN>
-static int launch_h(const ConvArgsH &a, hipStream_t st) {
-  constexpr int BN = WN * TN * 32;
-  ConvArgsH args = a;
-  args.n_row_tiles = (int)((a.n_out + BM - 1) / BM);
-  args.n_col_tiles = (a.cout + BN - 1) / BN;
-  const int ntiles = args.n_row_tiles * args.n_col_tiles;
-  const int grid = ((ntiles + 7) / 8) * 8;
-  hipLaunchKernelGGL((k_conv_f16x3<BM, KC, WM, WN, TM, TN>), dim3(grid, args.ksplit), dim3(HV_THREADS), 0, st, args);
-  PH_LAUNCH_CHECK();
-  if (args.ksplit > 1) {
-    const int64_t total = a.n_out * a.cout;
-    hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, args);
-    PH_LAUNCH_CHECK();
+// k_conv_h2 (mode 2) / k_conv_f16x3 (mode 1): tile height and stage depth from the step, tile width from cout
+static int ph_conv_h_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st) {
+  const bool pre = s.kernel == CONV_K_H2;
+  ConvKernelFn k = nullptr;
+#define PH_H2(KC_, BM_, WM_, WN_, TM_, TN_)                                                                                    \
+  (s.emit ? k_conv_h2<BM_, KC_, WM_, WN_, TM_, TN_, true> : k_conv_h2<BM_, KC_, WM_, WN_, TM_, TN_, false>)
+#define PH_H_CASE(BM_, WM_, WN_, TM_, TN_)                                                                                     \
+  if (s.bm == BM_) {                                                                                                           \
+    if (pre) k = s.kc == 64 ? PH_H2(64, BM_, WM_, WN_, TM_, TN_) : PH_H2(32, BM_, WM_, WN_, TM_, TN_);                         \
+    else k = s.kc == 64 ? k_conv_f16x3<BM_, 64, WM_, WN_, TM_, TN_> : k_conv_f16x3<BM_, 32, WM_, WN_, TM_, TN_>;               \
   }
-  ph_record_cfg(1, BM, BN, KC, args.ksplit, 0, 1, 4);
-  return 0;
+  if (s.bn == 32) {
+    PH_H_CASE(128, 4, 1, 1, 1);
+  } else if (s.bn == 64) {
+    PH_H_CASE(128, 4, 1, 1, 2);
+    PH_H_CASE(64, 2, 2, 1, 1);
+  } else {
+    PH_H_CASE(128, 2, 2, 2, 2);
+    PH_H_CASE(64, 2, 2, 1, 2);
+    PH_H_CASE(32, 1, 4, 1, 1);
+  }
+#undef PH_H_CASE
+#undef PH_H2
+  if (k == nullptr) {
+    ph_set_error("conv_fwd(f16x3): no kernel for bm=%d bn=%d", s.bm, s.bn);
+    return 1;
+  }
+  return ph_launch_tiles(k, a, s, st);
 }
 
-template <int BM, int KC, int WM, int WN, int TM, int TN>
-static int launch_h2(const ConvArgsH &a, hipStream_t st) {
-  constexpr int BN = WN * TN * 32;
-  ConvArgsH args = a;
-  args.n_row_tiles = (int)((a.n_out + BM - 1) / BM);
-  args.n_col_tiles = (a.cout + BN - 1) / BN;
-  const int ntiles = args.n_row_tiles * args.n_col_tiles;
-  const int grid = ((ntiles + 7) / 8) * 8;
-  if (args.out_split != nullptr && args.ksplit == 1)
-    hipLaunchKernelGGL((k_conv_h2<BM, KC, WM, WN, TM, TN, true>), dim3(grid, 1), dim3(HV_THREADS), 0, st, args);
-  else
-    hipLaunchKernelGGL((k_conv_h2<BM, KC, WM, WN, TM, TN, false>), dim3(grid, args.ksplit), dim3(HV_THREADS), 0, st, args);
-  PH_LAUNCH_CHECK();
-  if (args.ksplit > 1) {
-    const int64_t total = a.n_out * a.cout;
-    hipLaunchKernelGGL(k_splitk_epilogue, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, args);
-    PH_LAUNCH_CHECK();
+// The development switches of the dispatch (conv_plan.h: ConvKnobs), read ONCE when the library first launches a split
+// convolution.  PH_DEV_ENV answers "unset" in the product library: every field keeps its default there.
+static ConvKnobs conv_knobs_from_env() {
+  ConvKnobs k;
+  auto on = [](const char *e, bool dflt) { return e == nullptr ? dflt : atoi(e) != 0; };
+  if (const char *e = PH_DEV_ENV("PASCO_CONV_DMA")) {
+    k.dma_on = atoi(e) != 0;
+    k.dma_all = atoi(e) == 2;
   }
-  ph_record_cfg(2, BM, BN, KC, args.ksplit, (args.out_split != nullptr && args.ksplit == 1) ? 1 : 0, 2, 4);
-  return 0;
-}
-
-// Tuning overrides (development only), read ONCE when the library first launches a split convolution:
-//   PASCO_CONVH_MID=0      disable the 64-row / 64-channel-stage choice for thin 128-channel layers
-//   PASCO_CONVH_CFG=bm,kc  force tile height / stage depth where the shape allows it
-//   PASCO_CONVH_KSPLIT=n   force the split over the kernel offsets
-struct ConvHKnobs {
-  bool mid_on = true;
-  bool has_cfg = false;
-  int cfg_bm = 0, cfg_kc = 0;
-  bool has_ksplit = false;
-  int ksplit = 0;
-  bool dma_all = false;
-  bool win_on = true;      // PASCO_CONV_WIN=0: no LDS-window kernel
-  bool win_wide = false;   // PASCO_CONV_WIN=2: also on 128-wide tiles
-  bool rl_on = true;       // PASCO_CONV_RL=0: ignore row lists (walk all offsets of one-pair maps)
-  bool dma_on = true;      // PASCO_CONV_DMA=0: keep every launch on the register-staged k_conv_h2 (A/B comparisons)
-  bool wide_on = true;     // PASCO_CONV_WIDE=0: no 256 x 256 tiles (conv_wide.hip) for the 256-output-channel gather launches
-  ConvHKnobs() {
-    if (const char *e = PH_DEV_ENV("PASCO_CONV_DMA")) {
-      dma_on = atoi(e) != 0;
-      dma_all = atoi(e) == 2;      // 2: every tile width on the DMA kernel
-    }
-    if (const char *e = PH_DEV_ENV("PASCO_CONV_WIDE")) wide_on = atoi(e) != 0;
-    if (const char *e = PH_DEV_ENV("PASCO_CONVH_MID")) mid_on = atoi(e) != 0;
-    if (const char *e = PH_DEV_ENV("PASCO_CONV_WIN")) {
-      win_on = atoi(e) != 0;
-      win_wide = atoi(e) == 2;
-    }
-    if (const char *e = PH_DEV_ENV("PASCO_CONV_RL")) rl_on = atoi(e) != 0;
-    if (const char *e = PH_DEV_ENV("PASCO_CONVH_CFG")) has_cfg = sscanf(e, "%d,%d", &cfg_bm, &cfg_kc) >= 1;
-    if (const char *e = PH_DEV_ENV("PASCO_CONVH_KSPLIT")) {
-      has_ksplit = true;
-      ksplit = atoi(e);
-    }
+  if (const char *e = PH_DEV_ENV("PASCO_CONV_WIN")) {
+    k.win_on = atoi(e) != 0;
+    k.win_wide = atoi(e) == 2;
   }
-};
-static const ConvHKnobs &convh_knobs() {
-  static const ConvHKnobs k;
+  k.wide_on = on(PH_DEV_ENV("PASCO_CONV_WIDE"), true);
+  k.mid_on = on(PH_DEV_ENV("PASCO_CONVH_MID"), true);
+  k.rl_on = on(PH_DEV_ENV("PASCO_CONV_RL"), true);
+  if (const char *e = PH_DEV_ENV("PASCO_CONVH_CFG")) k.has_cfg = sscanf(e, "%d,%d", &k.cfg_bm, &k.cfg_kc) >= 1;
+  if (const char *e = PH_DEV_ENV("PASCO_CONVH_KSPLIT")) {
+    k.has_ksplit = true;
+    k.ksplit = atoi(e);
+  }
+  k.ksplit_model = on(PH_DEV_ENV("PASCO_CONVH_KSPLIT_MODEL"), true);
+  k.tail_on = on(PH_DEV_ENV("PASCO_CONV_TAIL"), true);
+  k.dma_inter = on(PH_DEV_ENV("PASCO_CONV_DMA_INTER"), true);
+  k.wop2 = on(PH_DEV_ENV("PASCO_WOP"), true);
+  if (const char *e = PH_DEV_ENV("PASCO_CONV_LIN")) k.lin_on = atoi(e);
+  if (const char *e = PH_DEV_ENV("PASCO_GRID_KS")) k.grid_ks = atoi(e);
+  k.grid_upw = on(PH_DEV_ENV("PASCO_GRID_UPW"), true);
   return k;
 }
+#ifdef PH_DEV
+// development build only: tools/ write the experiment state into the knobs (same-process A/B runs)
+static ConvKnobs &conv_knobs() {
+  static ConvKnobs k = conv_knobs_from_env();
+  return k;
+}
+extern "C" void ph_conv_dma_set_ablate(int mask) {      // bits 0..7: k_conv_dma / window kernels; bit 8: 256-row tiles of k_conv_dma
+  conv_knobs().dma_ablate = mask & 0xff;
+  conv_knobs().dma_tall = (mask & 0x100) != 0;
+}
+extern "C" void ph_conv_lin_set(int on) { conv_knobs().lin_on = on; }
+extern "C" void ph_conv_grid_set_ablate(int mask) { conv_knobs().grid_ablate = mask; }
+#else
+static const ConvKnobs &conv_knobs() {
+  static const ConvKnobs k = conv_knobs_from_env();
+  return k;
+}
+#endif
 
-// called from ph_conv_fwd (conv.hip) when desc->mma_mode is 1 or 2
-int ph_conv_fwd_f16x3(const ph_conv_desc *d, hipStream_t st) {
-  const bool pre = d->mma_mode == 2;
-  PH_REQUIRE(d->cin % 8 == 0 && d->cout % 4 == 0, "conv_fwd(f16x3): needs cin %% 8 == 0 and cout %% 4 == 0");
-  if (pre) {
-    PH_REQUIRE(d->in_split && d->w_split, "conv_fwd(f16x3, mode 2): pre-split operands missing");
-    PH_REQUIRE((((uintptr_t)d->in_split | (uintptr_t)d->w_split) & 15) == 0, "conv_fwd(f16x3): 16-byte alignment");
-    PH_REQUIRE(d->n_in < ((int64_t)1 << 31), "conv_fwd(f16x3): n_in too large");
-    PH_REQUIRE((((uintptr_t)d->out | (uintptr_t)d->residual | (uintptr_t)d->splitk_ws) & 15) == 0,
-               "conv_fwd(f16x3, mode 2): out / residual / splitk_ws must be 16-byte aligned");
-  } else {
-    PH_REQUIRE(d->w_f16_hi && d->w_f16_lo, "conv_fwd(f16x3): pre-split weights missing");
-    PH_REQUIRE((((uintptr_t)d->in | (uintptr_t)d->w_f16_hi | (uintptr_t)d->w_f16_lo) & 15) == 0,
-               "conv_fwd(f16x3): 16-byte alignment");
-  }
-  ConvArgsH a;
-  a.in_split = (const _Float16 *)d->in_split;
-  a.w_split = (const _Float16 *)d->w_split;
-  a.w_frag = (const _Float16 *)d->w_frag;
-  a.cpad = (d->cin + 31) / 32 * 32;
-  a.out_split = (_Float16 *)d->out_split;
-  a.osp_scale = d->osp_scale;
-  a.osp_shift = d->osp_shift;
-  a.osp_has = (d->osp_scale || d->osp_shift || d->osp_act != PH_ACT_NONE) ? 1 : 0;
-  a.osp_neg = d->osp_act == PH_ACT_RELU ? 0.f : (d->osp_act == PH_ACT_LEAKY ? d->epi_slope : 1.f);
-  PH_REQUIRE(d->split_exp2 >= -16 && d->split_exp2 <= 16, "conv_fwd(f16x3): split_exp2 out of range (%d)", d->split_exp2);
-  a.act_pow2 = ldexpf(1.f, d->split_exp2);
-  {   // the epilogue reads the per-channel vectors as float4 when all of them allow it
-    uintptr_t bits = 0;
-    const float *vecs[] = {d->bias, d->epi_scale, d->epi_shift, d->epi2_scale, d->epi2_shift, d->osp_scale, d->osp_shift};
-    for (const float *v : vecs) bits |= (uintptr_t)v;
-    a.par_vec = ((bits & 15) == 0 && d->cout % 4 == 0) ? 1 : 0;
-  }
-  if (d->out_split) {
-    PH_REQUIRE(pre, "conv_fwd(f16x3): out_split needs mma_mode 2");
-    PH_REQUIRE(d->cout % 32 == 0 && (((uintptr_t)d->out_split) & 15) == 0, "conv_fwd(f16x3): out_split needs cout %% 32 == 0");
-  }
-  PH_REQUIRE(d->out || d->out_split, "conv_fwd(f16x3): no output buffer");
+// the kernel argument block of the whole map: ConvArgsH a{} + the non-zero fields (the steps of the plan fill in their own)
+static ConvArgsH conv_args(const ph_conv_desc *d) {
+  ConvArgsH a{};
   a.in = d->in;
   a.w_hi = (const _Float16 *)d->w_f16_hi;
   a.w_lo = (const _Float16 *)d->w_f16_lo;
@@ -693,199 +657,141 @@ int ph_conv_fwd_f16x3(const ph_conv_desc *d, hipStream_t st) {
   a.epi2_scale = d->epi2_scale;
   a.epi2_shift = d->epi2_shift;
   a.residual = d->residual;
-  auto neg_of = [&](int act) { return act == PH_ACT_RELU ? 0.f : (act == PH_ACT_LEAKY ? d->epi_slope : 1.f); };
-  a.pro_neg = neg_of(d->pro_act);
-  a.epi_neg = neg_of(d->epi_act);
-  a.res_neg = neg_of(d->res_act);
+  a.pro_neg = neg_of(d->pro_act, d->epi_slope);
+  a.epi_neg = neg_of(d->epi_act, d->epi_slope);
+  a.res_neg = neg_of(d->res_act, d->epi_slope);
   a.w_unscale = d->w_unscale;
   a.has_pro = (d->pro_scale || d->pro_shift || d->pro_act != PH_ACT_NONE) ? 1 : 0;   // mode 2: already applied by ph_split_rows
   a.has_tail = (d->residual || d->epi2_scale || d->epi2_shift || d->res_act != PH_ACT_NONE || d->axis_table) ? 1 : 0;
+  a.status = d->status;
+  a.ksplit = 1;
+  a.in_split = (const _Float16 *)d->in_split;
+  a.w_split = (const _Float16 *)d->w_split;
+  a.w_frag = (const _Float16 *)d->w_frag;
+  a.cpad = (d->cin + 31) / 32 * 32;
+  a.out_split = (_Float16 *)d->out_split;
+  a.osp_scale = d->osp_scale;
+  a.osp_shift = d->osp_shift;
+  a.osp_neg = neg_of(d->osp_act, d->epi_slope);
+  a.osp_has = (d->osp_scale || d->osp_shift || d->osp_act != PH_ACT_NONE) ? 1 : 0;
+  a.act_pow2 = ldexpf(1.f, d->split_exp2);
+  a.route = d->route;
+  a.win_rows = d->win_rows;
+  a.win_cnt = d->win_cnt;
+  a.win_slots = d->win_slots;
   a.axis_table = d->axis_table;
   a.axis_coords = d->axis_coords;
   a.axis_lo = d->axis_lo;
   a.axis_rows = d->axis_rows;
+  {   // the epilogue reads the per-channel vectors as float4 when all of them allow it
+    uintptr_t bits = 0;
+    const float *vecs[] = {d->bias, d->epi_scale, d->epi_shift, d->epi2_scale, d->epi2_shift, d->osp_scale, d->osp_shift};
+    for (const float *v : vecs) bits |= (uintptr_t)v;
+    a.par_vec = ((bits & 15) == 0 && d->cout % 4 == 0) ? 1 : 0;
+  }
+  a.tail_ws = d->splitk_ws;
+  a.tail_ws_bytes = d->splitk_ws_bytes;
+  for (int q = 0; q < 4; ++q) a.gdim[q] = d->grid_dims[q];
+  for (int q = 0; q < 3; ++q) a.gker[q] = d->grid_kernel[q];
+  a.nbr_stride = d->n_out;
+  return a;
+}
+
+// what the planner branches on (conv_plan.h)
+static ConvShape conv_shape(const ph_conv_desc *d, bool have_zero_line) {
+  ConvShape s;
+  s.mma_mode = d->mma_mode;
+  s.n_in = d->n_in, s.n_out = d->n_out;
+  s.cin = d->cin, s.cout = d->cout, s.kvol = d->kvol, s.route = d->route;
+  s.ws_bytes = d->splitk_ws != nullptr ? d->splitk_ws_bytes : 0;
+  s.nbr = d->nbr != nullptr, s.out = d->out != nullptr, s.out_split = d->out_split != nullptr, s.w_frag = d->w_frag != nullptr;
+  s.axis = d->axis_table != nullptr, s.residual = d->residual != nullptr;
+  s.win = d->win_rows && d->win_cnt && d->win_slots && d->win_stats;
+  s.rl = d->rl_in && d->rl_out && d->rl_tile_k;
+  s.rl_rows = d->rl_rows;
+  for (int q = 0; q < 4; ++q) s.grid_dims[q] = d->grid_dims[q];
+  for (int q = 0; q < 3; ++q) s.grid_kernel[q] = d->grid_kernel[q];
+  s.have_zero_line = have_zero_line;
+  return s;
+}
+
+// the argument block of one step: its rows, its slice count, and what only its kernel reads
+static ConvArgsH step_args(const ConvArgsH &map, const ph_conv_desc *d, const ConvStep &s, const char *zero) {
+  ConvArgsH a = row_range(map, s.row0, s.rows);
+  if (s.rowlist) {          // outputs go to the rows the list names
+    a.nbr = d->rl_in;
+    a.out_rows = d->rl_out;
+    a.tile_k = d->rl_tile_k;
+  }
+  a.ksplit = s.ksplit;
+  a.partial = s.use_ws ? (float *)d->splitk_ws : nullptr;
+  a.grid_upw = s.grid_upw;
+  if (s.win_pair) {
+    a.win_stats = d->win_stats;
+    a.win_which = s.win_which;
+    a.win_gather = s.win_gather;
+  }
+  if (s.kernel == CONV_K_DMA || s.kernel == CONV_K_WIDE || s.kernel == CONV_K_WIN || s.kernel == CONV_K_WOP2) a.zero = zero;
+  a.ablate = s.ablate;
+  if (s.no_axis) a.axis_table = nullptr;
+  if (s.no_residual) a.residual = nullptr;
+  return a;
+}
+
+// called from ph_conv_fwd (conv.hip) when desc->mma_mode is 1 or 2: validate, build the argument block, plan (conv_plan.h: the
+// order of the routes and every rule), run the steps
+int ph_conv_fwd_f16x3(const ph_conv_desc *d, hipStream_t st) {
+  const bool pre = d->mma_mode == 2;
+  PH_REQUIRE(d->cin % 8 == 0 && d->cout % 4 == 0, "conv_fwd(f16x3): needs cin %% 8 == 0 and cout %% 4 == 0");
+  if (pre) {
+    PH_REQUIRE(d->in_split && d->w_split, "conv_fwd(f16x3, mode 2): pre-split operands missing");
+    PH_REQUIRE((((uintptr_t)d->in_split | (uintptr_t)d->w_split) & 15) == 0, "conv_fwd(f16x3): 16-byte alignment");
+    PH_REQUIRE(d->n_in < ((int64_t)1 << 31), "conv_fwd(f16x3): n_in too large");
+    PH_REQUIRE((((uintptr_t)d->out | (uintptr_t)d->residual | (uintptr_t)d->splitk_ws) & 15) == 0,
+               "conv_fwd(f16x3, mode 2): out / residual / splitk_ws must be 16-byte aligned");
+  } else {
+    PH_REQUIRE(d->w_f16_hi && d->w_f16_lo, "conv_fwd(f16x3): pre-split weights missing");
+    PH_REQUIRE((((uintptr_t)d->in | (uintptr_t)d->w_f16_hi | (uintptr_t)d->w_f16_lo) & 15) == 0,
+               "conv_fwd(f16x3): 16-byte alignment");
+  }
+  PH_REQUIRE(d->split_exp2 >= -16 && d->split_exp2 <= 16, "conv_fwd(f16x3): split_exp2 out of range (%d)", d->split_exp2);
+  if (d->out_split) {
+    PH_REQUIRE(pre, "conv_fwd(f16x3): out_split needs mma_mode 2");
+    PH_REQUIRE(d->cout % 32 == 0 && (((uintptr_t)d->out_split) & 15) == 0, "conv_fwd(f16x3): out_split needs cout %% 32 == 0");
+  }
+  PH_REQUIRE(d->out || d->out_split, "conv_fwd(f16x3): no output buffer");
   if (d->axis_table) {
     PH_REQUIRE(pre, "conv_fwd: axis_table needs mma_mode 2");
     PH_REQUIRE(d->axis_coords && d->axis_rows > 0 && d->cout % 4 == 0 && (((uintptr_t)d->axis_table | (uintptr_t)d->axis_coords) & 15) == 0,
                "conv_fwd: axis_table needs axis_coords, axis_rows > 0, 16-byte alignment");
   }
-  a.n_row_tiles = a.n_col_tiles = 0;
-  a.status = d->status;
-  a.zero = nullptr;
-  a.ablate = 0;
-  a.route = d->route;
-  a.out_rows = nullptr;
-  a.tile_k = nullptr;
-  a.nbr_stride = d->n_out;
-  for (int q = 0; q < 4; ++q) a.gdim[q] = d->grid_dims[q];
-  for (int q = 0; q < 3; ++q) a.gker[q] = d->grid_kernel[q];
-  a.grid_upw = 0;
-  a.tail_ws = d->splitk_ws;
-  a.tail_ws_bytes = d->splitk_ws_bytes;
-  a.win_rows = d->win_rows;
-  a.win_cnt = d->win_cnt;
-  a.win_slots = d->win_slots;
-  a.win_stats = nullptr;
-  a.win_which = 0;
-  a.win_gather = 0;
-  const int bn = d->cout <= 32 ? 32 : (d->cout <= 64 ? 64 : 128);
-  const int64_t ncol = (d->cout + bn - 1) / bn;
-  // tile height: the tallest tile that still gives >= 2 workgroups per CU (profiles/r1e_op_bench.json)
-  int bm = 128;
-  if (bn >= 64 && ((d->n_out + 127) / 128) * ncol < 2 * 256) bm = 64;
-  if (bn == 128 && bm == 64 && ((d->n_out + 63) / 64) * ncol < 2 * 256) bm = 32;
-  int kc = (d->cin % 64 == 0 && d->cin >= 256) ? 64 : 32;   // deeper stages pay only for wide layers (profiles/r1f_op_bench.json)
-  // 128-channel layers with fewer than ~1.5 waves of 128-row tiles (stride-2 levels of the pruned scene): 64-row
-  // tiles with 64-channel stages measured 304 -> 250 us (profiles/README.md, r1k sweep); env PASCO_CONVH_MID=0 disables
-  const ConvHKnobs &knobs = convh_knobs();
-  if (pre && knobs.mid_on && bn == 128 && d->cin == 128 && d->kvol > 1 && ((d->n_out + 127) / 128) * ncol < 3 * 256) {
-    if (bm == 128) bm = 64;
-    kc = 64;
+  const ConvArgsH map = conv_args(d);
+  // 256 zero bytes of device memory for absent neighbours; without them the planner declines the kernels that read them
+  const char *zero = pre ? ph_dma_zero_line() : nullptr;
+  const ConvPlan plan = conv_plan(conv_shape(d, zero != nullptr), conv_knobs());
+  if (plan.error == CONV_PLAN_NO_ZERO_LINE) {
+    ph_set_error("conv_fwd(windows): no zero line");
+    return 2;
   }
-  if (pre && a.cpad % 64 != 0) kc = 32;
-  const bool env = knobs.has_cfg;
-  if (env) {
-    const int em = knobs.cfg_bm, ek = knobs.cfg_kc;
-    if (em == 128 || (em == 64 && bn >= 64) || (em == 32 && bn == 128)) bm = em;
-    if (ek == 32 || (ek == 64 && (!pre || a.cpad % 64 == 0))) kc = ek;
-  }
-  // Few-row layers (dense bottleneck: 245 offsets on 6.7 k rows; stride-4/8 layers): every workgroup streams
-  // the whole W[k] slab sequence from L2, so small row tiles multiply the weight traffic.  Keep the tall
-  // 128-row tile and get the parallelism from a split over the kernel offsets instead (partial sums reduced
-  // in a fixed order by k_splitk_epilogue).  The caller provides the scratch (desc->splitk_ws), else no split.
-  a.ksplit = 1;
-  a.partial = nullptr;
-  {
-    const bool se = knobs.has_ksplit;
-    const int64_t t128 = ((d->n_out + 127) / 128) * ncol;
-    int want = (int)(2048 / (t128 > 0 ? t128 : 1));
-    if (want > 8) want = 8;
-    if (want > d->kvol / 4) want = d->kvol / 4;
-    // round 3: the number of slices by a cost model instead (128-wide tiles; both operand modes, so that they keep choosing alike): the launch runs in
-    // ceil(tiles x slices / 512) rounds of resident workgroups, a round lasts as long as its longest slice, and every slice
-    // adds a partial-sum round trip - e.g. 146 tiles x 27 offsets: 6 slices = 2 rounds of 5 offsets, 3 slices = ONE round of 9
-    // (profiles/r3z_layer_ab_ksplit_model.txt).  PASCO_CONVH_KSPLIT_MODEL=0: the rule above.
-    static const bool model_on = [] { const char *e = PH_DEV_ENV("PASCO_CONVH_KSPLIT_MODEL"); return e == nullptr || atoi(e) != 0; }();
-    if (model_on && bn == 128 && t128 < 2 * 256 && d->kvol >= 8 && d->splitk_ws != nullptr) {
-      const double stage_us = 1.3, fixed_us = 5.0;           // one 32-channel stage of a workgroup sharing its CU; launch / prologue
-      const double nchunks = (double)(a.cpad / 32);
-      int best = 1;
-      double best_us = 1e30;
-      for (int ks = 1; ks <= 12 && ks <= d->kvol / 3; ++ks) {
-        const int kper = (d->kvol + ks - 1) / ks;
-        if (kper > (d->kvol > 100 ? 31 : 32) || (d->kvol + kper - 1) / kper != ks) continue;   // beyond the index table (the dense
-                                                       // GEMMs keep its last slot for their stage list, conv_dma.hip) / same as fewer slices
-        if (ks > 1 && d->splitk_ws_bytes < (int64_t)ks * d->n_out * d->cout * 4) continue;
-        const double rounds = (double)((t128 * ks + 511) / 512);
-        double us = rounds * (kper * nchunks * stage_us + fixed_us);
-        if (ks > 1) us += (double)ks * (double)d->n_out * d->cout * 4.0 / 3.0e6 + fixed_us;   // the reduction: 3 TB/s
-        if (us < best_us) best_us = us, best = ks;
-      }
-      want = best;
+  for (int i = 0; i < plan.nsteps; ++i) {
+    const ConvStep &s = plan.step[i];
+    const ConvArgsH a = step_args(map, d, s, zero);
+    int rc;
+    switch (s.kernel) {
+      case CONV_K_DMA: rc = ph_conv_dma_launch(a, s, st); break;
+      case CONV_K_WIDE: rc = ph_conv_wide_launch(a, s, st); break;
+      case CONV_K_LIN: rc = ph_conv_lin_launch(a, s, st); break;
+      case CONV_K_GRID: rc = ph_conv_grid_launch(a, s, st); break;
+      case CONV_K_WIN: rc = ph_conv_win_launch(a, s, st); break;
+      case CONV_K_WOP2: rc = ph_conv_wop2_launch(a, s, st); break;
+      default: rc = ph_conv_h_launch(a, s, st); break;
     }
-    if (se) want = knobs.ksplit;
-    const bool room = d->splitk_ws != nullptr && d->splitk_ws_bytes >= (int64_t)want * d->n_out * d->cout * 4;
-    if (bn == 128 && t128 < 2 * 256 && want >= 2 && room && !env) {
-      bm = 128;
-      a.ksplit = want;
-      a.partial = (float *)d->splitk_ws;
-    } else if (se && want >= 2 && room) {
-      a.ksplit = want;
-      a.partial = (float *)d->splitk_ws;
+    if (rc) return rc;
+    if (s.ksplit > 1) {
+      if (int rc2 = ph_launch_splitk_epilogue(a, st)) return rc2;
     }
   }
-  // the dense-grid promise (the bottleneck's implicit GEMMs): windows of the input instead of gathers, its own split over the units
-  if (pre && !env && d->grid_dims[0] > 0 && d->nbr != nullptr) {
-    const int rc = ph_conv_grid_try(a, st);
-    if (rc >= 0) return rc;
-  }
-  // one-pair-per-row maps with row lists (generative transposed convolutions): every 128-position tile of the list is the
-  // k = 1 product of one kernel offset; outputs go to the rows the list names
-  if (pre && !env && d->rl_in && d->rl_out && d->rl_tile_k && d->rl_rows > 0 && knobs.rl_on && (bn == 64 || bn == 128)) {
-    ConvArgsH b = a;
-    b.nbr = d->rl_in;
-    b.out_rows = d->rl_out;
-    b.tile_k = d->rl_tile_k;
-    b.n_out = d->rl_rows;
-    b.ksplit = 1;
-    b.partial = nullptr;
-    b.win_stats = nullptr;
-    b.win_gather = 0;
-    const int rc = ph_conv_dma_try(b, bn, st);
-    if (rc == 0) ph_record_cfg(2, 128, bn, 32, 1, a.out_split != nullptr ? 1 : 0, 3, 4);
-    if (rc >= 0) return rc;
-  }
-  // 3x3x3 convolutions on big maps with window tables: launch the window kernel AND the gather kernel below; the
-  // device-side predicate (window passes per tile, ph_win_build) lets exactly one of them do the work.  Only where no
-  // split over the offsets was chosen (its reduction kernel would run unconditionally).
-  bool win_pair = false;
-  // Measured (profiles/README.md, round 2): 64-wide tiles 638 -> 540 us on the 683 k-row map (two workgroups per CU);
-  // 128-wide tiles lose to the gather kernel (one workgroup per CU: 668 vs 567 us) and stay there unless
-  // PASCO_CONV_WIN=2.
-  // (a 256-wide window workgroup for 256-channel layers was built and measured in round 2: 568 vs 547 us for the gather
-  // kernel - removed in round 5, profiles/README.md)
-  if (pre && knobs.win_on && !env && d->kvol == 27 &&
-      (bn == 64 || (bn == 128 && (knobs.win_wide || (d->route & PH_ROUTE_WIN_ALWAYS)))) &&
-      a.ksplit == 1 &&
-      d->win_rows && d->win_cnt && d->win_slots && d->win_stats) {
-    a.win_stats = d->win_stats;
-    a.win_which = (bn == 64 ? 0 : 1) | ph_win_force_bits(d->route);
-    a.win_gather = 0;
-    if (int rc = ph_conv_win_launch(a, bn, st)) return rc;
-    a.win_gather = 1;
-    win_pair = true;
-    if (bm != 128) bm = 128;   // pairs are only formed on big maps: the gather side keeps its 128-row tile
-  }
-  auto gather_launch = [&]() -> int {
-  // default for pre-split operands: the LDS-DMA pipelined kernel (conv_dma.hip; 128-row tiles, parallelism of few-row
-    // layers from the split over the offsets chosen above); it declines slices of more than 32 offsets
-    // measured (profiles/README.md, round 2): 6-9 % faster than k_conv_h2 on 128-channel-wide tiles, a few % slower on 64-wide
-    if (pre && knobs.wide_on && !env && bn == 128 && (d->cout == 256 || d->cout == 128) && d->kvol >= 8 && d->nbr != nullptr) {
-      const int rc = ph_conv_wide_try(a, st);
-      if (rc >= 0) return rc;
-    }
-    // k = 1 streams (linear layers, 1x1x1 convolutions) of 64 / 128 input channels onto 128-wide tiles: the row-stream kernel
-    if (pre && knobs.dma_on && !env && bn == 128 && d->kvol == 1 && a.ksplit == 1) {
-      const int rc = ph_conv_lin_try(a, st);
-      if (rc >= 0) return rc;
-    }
-    if (pre && knobs.dma_on && !env && (bn == 128 || knobs.dma_all)) {
-      ConvArgsH b = a;
-      if (bm != 128) {        // the choice above was made for a shorter tile: redo the split decision for 128 rows
-        const int64_t t128 = ((d->n_out + 127) / 128) * ncol;
-        int want = (int)(1024 / (t128 > 0 ? t128 : 1));
-        if (want > 8) want = 8;
-        if (want > d->kvol / 4) want = d->kvol / 4;
-        const bool room = d->splitk_ws != nullptr && d->splitk_ws_bytes >= (int64_t)want * d->n_out * d->cout * 4;
-        if (t128 < 256 && want >= 2 && room) {
-          b.ksplit = want;
-          b.partial = (float *)d->splitk_ws;
-        }
-      }
-      const int rc = ph_conv_dma_try(b, bn, st);
-      if (rc >= 0) return rc;
-    }
-#define PH_H_CASE(BM_, WM_, WN_, TM_, TN_)                                                                \
-    if (bm == BM_) {                                                                                        \
-      if (pre) return kc == 64 ? launch_h2<BM_, 64, WM_, WN_, TM_, TN_>(a, st) : launch_h2<BM_, 32, WM_, WN_, TM_, TN_>(a, st); \
-      return kc == 64 ? launch_h<BM_, 64, WM_, WN_, TM_, TN_>(a, st) : launch_h<BM_, 32, WM_, WN_, TM_, TN_>(a, st);            \
-    }
-    if (bn == 32) {
-      PH_H_CASE(128, 4, 1, 1, 1);
-    } else if (bn == 64) {
-      PH_H_CASE(128, 4, 1, 1, 2);
-      PH_H_CASE(64, 2, 2, 1, 1);
-    } else {
-      PH_H_CASE(128, 2, 2, 2, 2);
-      PH_H_CASE(64, 2, 2, 1, 2);
-      PH_H_CASE(32, 1, 4, 1, 1);
-    }
-#undef PH_H_CASE
-    ph_set_error("conv_fwd(f16x3): no kernel for bm=%d bn=%d", bm, bn);
-    return 1;
-  };
-  const int rc = gather_launch();
-  if (rc == 0 && win_pair)   // a window / gather pair: which one worked is the device's decision
-    ph_record_cfg(2, 128, bn, 32, 1, a.out_split != nullptr ? 1 : 0, 5, 4);
-  return rc;
+  const int *c = plan.cfg;
+  ph_record_cfg(c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);
+  return 0;
 }

@@ -394,93 +394,9 @@ __global__ void __launch_bounds__(512, 2) k_conv_grid(ConvArgsH a) {
   h2_store_tile<TM, TN, EMIT>(a, acc, m0, n0, wm, wn, h, l31);
 }
 
-#ifdef PH_DEV
-// development build only (tools/grid_ab.py): phase ablation of k_conv_grid - 1 window DMA, 2 weight DMA, 4 MFMAs, 8 fragment reads,
+// Which launches carry a usable dense-grid promise and how they are split over the units: conv_plan.h.  Development build
+// (tools/grid_ab.py, ph_conv_grid_set_ablate -> a.ablate): phase ablation - 1 window DMA, 2 weight DMA, 4 MFMAs, 8 fragment reads,
 // 16 no vmcnt wait, 32 no barrier, 64 no fragment-address update.  Wrong sums, right instruction stream otherwise.
-static int g_grid_ablate = 0;
-extern "C" void ph_conv_grid_set_ablate(int mask) { g_grid_ablate = mask; }
-#else
-constexpr int g_grid_ablate = 0;
-#endif
-
-// reachable (dx, dz) groups of an average tile: all dx, the dz that stay inside the grid
-static double grid_groups(const int *gd, const int *gk) {
-  double zavg = 0.0;
-  for (int z = 0; z < gd[3]; ++z)
-    for (int iz = 0; iz < gk[2]; ++iz) zavg += (z + iz - gk[2] / 2 >= 0 && z + iz - gk[2] / 2 < gd[3]) ? 1.0 : 0.0;
-  return gk[0] * zavg / gd[3];
-}
-
-// Serves mode-2 launches that carry the dense-grid promise (ph_conv_desc.grid_dims / grid_kernel) with 128 k output channels and whole
-// 32-channel chunks; -1 = not served (the caller goes on to the gather kernels, which read `nbr`).  The split over the units comes
-// from a cost model like ph_conv_fwd_f16x3's: rounds of one workgroup per CU x the longest slice + the reduction's round trip.
-int ph_conv_grid_try(const ConvArgsH &a_in, hipStream_t st) {
-  const int *gd = a_in.gdim, *gk = a_in.gker;
-  if (gd[0] <= 0 || a_in.tile_k != nullptr || a_in.win_gather || (a_in.cpad & 31) || a_in.cout % 128 != 0 || a_in.in_split == nullptr ||
-      a_in.axis_table != nullptr)
-    return -1;
-  if (a_in.route & PH_ROUTE_GRID_NEVER) return -1;
-  const int kx = gk[0], ky = gk[1], kz = gk[2];
-  if (ky < 3 || ky > 7 || !(kx & 1) || !(ky & 1) || !(kz & 1) || kx * kz > 64 || kx * ky * kz != a_in.kvol) return -1;
-  const int64_t sites = (int64_t)gd[0] * gd[1] * gd[2] * gd[3];
-  if (sites != a_in.n_out || sites != a_in.n_in || gd[2] < 1) return -1;
-  ConvArgsH a = a_in;
-  a.n_row_tiles = (int)((a.n_out + 255) / 256);
-  a.n_col_tiles = a.cout / 128;
-  const int64_t tiles = (int64_t)a.n_row_tiles * a.n_col_tiles;
-  const int nchunks = a.cpad >> 5;
-  const double units = grid_groups(gd, gk) * nchunks;
-  const double stage_us = 1.0, fixed_us = 8.0;
-  int best = 1;
-  double best_us = 1e30;
-  for (int ks = 1; ks <= 12; ++ks) {
-    if (ks > 1 && (a.tail_ws == nullptr || a.tail_ws_bytes < (int64_t)ks * a.n_out * a.cout * 4)) break;
-    if (ks > 1 && units / ks < 2.0) break;
-    const double rounds = (double)((tiles * ks + 255) / 256);
-    double us = rounds * (ceil(units / ks) * ky * stage_us + fixed_us);
-    if (ks > 1) us += (double)ks * (double)a.n_out * a.cout * 4.0 / 3.0e6 + 5.0;
-    if (us < best_us) best_us = us, best = ks;
-  }
-  if (const char *e = PH_DEV_ENV("PASCO_GRID_KS")) {              // development build: the number of slices by hand (tools/grid_ab.py)
-    const int ks = atoi(e);
-    if (ks >= 1 && (ks == 1 || (a.tail_ws != nullptr && a.tail_ws_bytes >= (int64_t)ks * a.n_out * a.cout * 4))) best = ks;
-  }
-  a.grid_upw = 0;
-  if (best > 1 && tiles * best <= 256) {
-    // ONE round of workgroups: the launch lasts as long as its longest workgroup, and the model's slices are for a tile with the
-    // AVERAGE number of reachable groups - tiles in the grid's inner z planes reach a third more, a tile across two planes more still.
-    // Aim at the same units per workgroup everywhere, with as many slices in the launch as the fullest tile takes (measured on
-    // the 75-offset launches: -5 .. -8 %).  Launches of several rounds balance by themselves - their workgroups are handed out as CUs
-    // fall free - and lose 12 % to the extra slices (245 offsets: 9 -> 12): profiles/r6w_grid_balance.txt
-    const int upw = (int)(units / best + 0.5) > 0 ? (int)(units / best + 0.5) : 1;
-    int zmax = 0;
-    for (int z = 0; z < gd[3]; ++z) {
-      int c = 0;
-      for (int iz = 0; iz < kz; ++iz) c += (z + iz - kz / 2 >= 0 && z + iz - kz / 2 < gd[3]) ? 1 : 0;
-      zmax = c > zmax ? c : zmax;
-    }
-    const int zreach = zmax + 1 < kz ? zmax + 1 : kz;               // a tile across a plane boundary
-    int ksmax = (kx * zreach * nchunks + upw / 2) / upw;
-    ksmax = ksmax > 12 ? 12 : ksmax;
-    while (ksmax > best && a.tail_ws_bytes < (int64_t)ksmax * a.n_out * a.cout * 4) --ksmax;
-    const char *e = PH_DEV_ENV("PASCO_GRID_UPW");                  // development build: 0 = the same slices for every tile
-    if (e == nullptr || atoi(e) != 0) {
-      if (ksmax > best) best = ksmax;
-      a.grid_upw = upw;
-    }
-  }
-  a.ksplit = best;
-  a.partial = best > 1 ? (float *)a.tail_ws : nullptr;
-  a.win_stats = nullptr;
-  a.ablate = g_grid_ablate;
-  const int grid = (int)((tiles + 7) / 8) * 8;
-  const bool emit = a.out_split != nullptr && a.ksplit == 1;
-  if (emit) hipLaunchKernelGGL((k_conv_grid<true>), dim3(grid, 1), dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((k_conv_grid<false>), dim3(grid, a.ksplit), dim3(512), 0, st, a);
-  PH_LAUNCH_CHECK();
-  if (a.ksplit > 1) {
-    if (int rc = ph_launch_splitk_epilogue(a, st)) return rc;
-  }
-  ph_record_cfg(2, 256, 128, 32, a.ksplit, emit ? 1 : 0, 8, 8);
-  return 0;
+int ph_conv_grid_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st) {
+  return ph_launch_tiles(s.emit ? k_conv_grid<true> : k_conv_grid<false>, a, s, st);
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include <type_traits>
 
+#include "conv_plan.h"
 #include "ph_common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -60,12 +61,12 @@ struct ConvArgsH {
   // row lists (ph_conv_desc.rl_*): output row of tile row r = out_rows[r] (-1 = padding), kernel offset of row tile t = tile_k[t]
   const int32_t *out_rows, *tile_k;
   int par_vec;                // every per-channel vector (bias, epi*, osp*) is 16-byte aligned: the epilogue loads them as float4
-  void *tail_ws;              // host-side only: the caller's split scratch (ph_conv_desc.splitk_ws) for ph_conv_dma_try's tail split
+  void *tail_ws;              // host-side only: the caller's split scratch (ph_conv_desc.splitk_ws)
   int64_t tail_ws_bytes;
   int gdim[4], gker[3];       // ph_conv_desc.grid_dims / grid_kernel (all zero: no dense-grid promise); conv_grid.hip
   int grid_upw;               // k_conv_grid: units of work per workgroup the launcher aims at (a tile takes round(its units / this) slices)
   int64_t nbr_stride;         // k_conv_dma: rows of one offset's segment of `nbr` (= the map's n_out; a launch over a row range of
-                              // the map has its own, smaller n_out and row-shifted pointers - ph_conv_dma_try's tail split)
+                              // the map has its own, smaller n_out and row-shifted pointers - row_range below)
 };
 
 // element offsets of the three table rows (x, y, z) of one output row (coordinates clamped to the table)
@@ -118,26 +119,45 @@ __device__ __forceinline__ bool ph_win_pred(const int32_t *stats, int which, int
   if (which & 0x200) return false;
   return (int64_t)stats[which & 1] * 4 <= n_row_tiles * 5;
 }
-// ph_conv_desc.route -> the predicate override bits of win_which
-static inline int ph_win_force_bits(int route) { return (route & PH_ROUTE_WIN_ALWAYS) ? 0x100 : ((route & PH_ROUTE_WIN_NEVER) ? 0x200 : 0); }
+// ---- host side: what the launchers of the kernel files and the executor (ph_conv_fwd_f16x3) share ----------------------------
+// Each kernel file exposes ONE launch function: it takes the step's prepared argument block and the step of the plan
+// (conv_plan.h), performs the template switch and launches.  The split's reduction and the config record are the executor's.
 // conv_dma.hip: 256 zero bytes of device memory for absent neighbours
 const char *ph_dma_zero_line();
-int ph_dma_ablate_bits();   // 0 in the product library (development build: tools/dma_ablate.py)
-// conv_win.hip
-int ph_conv_win_launch(const ConvArgsH &a, int bn, hipStream_t st);
-// conv_wop.hip: the window kernel of the 64-wide outputs (args.n_row_tiles set by the caller)
-int ph_conv_wop2_launch(const ConvArgsH &args, hipStream_t st);
+int ph_conv_dma_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st);
+int ph_conv_lin_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st);
+int ph_conv_wide_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st);
+int ph_conv_grid_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st);
+int ph_conv_win_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st);
+int ph_conv_wop2_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st);
 
-// conv_f16x3.hip: reduction + epilogue of a split over the kernel offsets (after a launch with args.ksplit > 1)
-int ph_launch_splitk_epilogue(const ConvArgsH &args, hipStream_t st);
-// conv_dma.hip: the LDS-DMA pipelined kernel; -1 = shape not served (caller falls back to k_conv_h2)
-int ph_conv_dma_try(const ConvArgsH &a, int bn, hipStream_t st);
-// conv_lin.hip: k = 1 products of 64 / 128 input channels as a row stream (weights in LDS, no barriers); -1 = shape not served
-int ph_conv_lin_try(const ConvArgsH &a, hipStream_t st);
-// conv_wide.hip: 256 x 256 tiles, 8 waves, one workgroup per CU (256 output channels); -1 = shape not served
-int ph_conv_wide_try(const ConvArgsH &a, hipStream_t st);
-// conv_grid.hip: launches with the dense-grid promise (a.gdim), activations from LDS windows; -1 = shape not served
-int ph_conv_grid_try(const ConvArgsH &a, hipStream_t st);
+// negative-side factor of a fused activation (ph_act): 1 none, 0 ReLU, slope leaky
+static inline float neg_of(int act, float slope) { return act == PH_ACT_RELU ? 0.f : (act == PH_ACT_LEAKY ? slope : 1.f); }
+
+// the launch over output rows [r0, r0 + rows) of the map: its own n_out and row-shifted pointers; `nbr_stride` stays the map's
+static inline ConvArgsH row_range(const ConvArgsH &a, int64_t r0, int64_t rows) {
+  ConvArgsH v = a;
+  v.n_out = rows;
+  if (v.nbr) v.nbr = a.nbr + r0;
+  if (v.out) v.out = a.out + r0 * a.cout;
+  if (v.out_split) v.out_split = a.out_split + r0 * a.cout * 2;
+  if (v.residual) v.residual = a.residual + r0 * a.cout;
+  if (v.axis_coords) v.axis_coords = a.axis_coords + r0 * 4;
+  return v;
+}
+
+// one launch of a tiled kernel: the grid padded to whole groups of 8 workgroups (the XCD-aware tile order), blockIdx.y = the
+// slices of the split unless the launch emits
+typedef void (*ConvKernelFn)(ConvArgsH);
+static inline int ph_launch_tiles(ConvKernelFn kernel, const ConvArgsH &a, const ConvStep &s, hipStream_t st) {
+  ConvArgsH args = a;
+  args.n_row_tiles = (int)conv_tiles(a.n_out, s.bm);
+  args.n_col_tiles = (int)conv_tiles(a.cout, s.bn);
+  const int grid = (args.n_row_tiles * args.n_col_tiles + 7) / 8 * 8;
+  hipLaunchKernelGGL(kernel, dim3(grid, s.emit ? 1 : args.ksplit), dim3(s.waves * 64), 0, st, args);
+  PH_LAUNCH_CHECK();
+  return 0;
+}
 
 // hi / lo halves of four values -> the [hi x32 | lo x32] group layout (dst points at the run's hi slot)
 __device__ __forceinline__ bool emit_split4(const float v[4], const float *sc, const float *sh, int has, float neg,

@@ -150,42 +150,26 @@ __global__ void __launch_bounds__(LIN_NT, 2) k_conv_lin(ConvArgsH a) {
   }
 }
 
-// ph_conv_desc.route & PH_ROUTE_LIN_NEVER sends a launch back to k_conv_dma (tests/test_hip_lin.py: the two are bit-identical).
-// Development build: PASCO_CONV_LIN=0 / ph_conv_lin_set for same-process A/B runs (bits: 0 = on, 8.. = workgroups per CU)
-#ifdef PH_DEV
-static int g_lin_on = [] { const char *e = PH_DEV_ENV("PASCO_CONV_LIN"); return e == nullptr ? 1 : atoi(e); }();
-extern "C" void ph_conv_lin_set(int on) { g_lin_on = on; }
-#else
-constexpr int g_lin_on = 1;
-#endif
-
-// Takes k = 1 launches on pre-split operands with 64 or 128 (padded) input channels; -1 = not served.
-int ph_conv_lin_try(const ConvArgsH &a_in, hipStream_t st) {
-  if (!(g_lin_on & 1) || (a_in.route & PH_ROUTE_LIN_NEVER)) return -1;
-  if (a_in.kvol != 1 || a_in.ksplit != 1 || a_in.tile_k != nullptr || a_in.out_rows != nullptr) return -1;
-  if (a_in.in_split == nullptr || a_in.w_split == nullptr || (a_in.cpad != 64 && a_in.cpad != 128)) return -1;
-  if (a_in.n_out < 1) return -1;
+// k = 1 launches on pre-split operands with 64 or 128 (padded) input channels (conv_plan.h; PH_ROUTE_LIN_NEVER sends a launch back
+// to k_conv_dma - tests/test_hip_lin.py: the two are bit-identical).
+int ph_conv_lin_launch(const ConvArgsH &a_in, const ConvStep &s, hipStream_t st) {
   ConvArgsH a = a_in;
-  a.ablate = 0;
-  a.n_col_tiles = (a.cout + LIN_BN - 1) / LIN_BN;
+  a.n_col_tiles = (int)conv_tiles(a.cout, LIN_BN);
   const int64_t nblk = (a.n_out + 31) / 32;
-  const bool emit = a.out_split != nullptr;
-  // every workgroup stages the weight tile once: as many workgroups as stay resident (2 per CU), fewer for short launches
-  const int per_cu = (g_lin_on >> 8) & 15;
-  const int wpc = per_cu ? per_cu : 2;          // 206 - 256 registers: two waves per SIMD
-  int64_t gx = (256 * (int64_t)wpc) / a.n_col_tiles;
+  // every workgroup stages the weight tile once: as many workgroups as stay resident (2 per CU: 206 - 256 registers, two waves
+  // per SIMD), fewer for short launches
+  int64_t gx = (256 * (int64_t)s.lin_wpc) / a.n_col_tiles;
   const int64_t need = (nblk + 3) / 4;
   if (gx > need) gx = need;
   if (gx < 1) gx = 1;
   const dim3 grid((unsigned)gx, (unsigned)a.n_col_tiles);
   if (a.cpad == 64) {
-    if (emit) hipLaunchKernelGGL((k_conv_lin<2, true>), grid, dim3(LIN_NT), 0, st, a);
+    if (s.emit) hipLaunchKernelGGL((k_conv_lin<2, true>), grid, dim3(LIN_NT), 0, st, a);
     else hipLaunchKernelGGL((k_conv_lin<2, false>), grid, dim3(LIN_NT), 0, st, a);
   } else {
-    if (emit) hipLaunchKernelGGL((k_conv_lin<4, true>), grid, dim3(LIN_NT), 0, st, a);
+    if (s.emit) hipLaunchKernelGGL((k_conv_lin<4, true>), grid, dim3(LIN_NT), 0, st, a);
     else hipLaunchKernelGGL((k_conv_lin<4, false>), grid, dim3(LIN_NT), 0, st, a);
   }
   PH_LAUNCH_CHECK();
-  ph_record_cfg(2, 32, LIN_BN, 32, 1, emit ? 1 : 0, 7, 4);
   return 0;
 }

@@ -24,6 +24,7 @@
 #include "conv_h2_common.h"
 
 constexpr int WIDE_KMAX = 27;     // kernel offsets one workgroup walks (index table in LDS); more -> split over the offsets
+static_assert(WIDE_KMAX == CONV_WIDE_KMAX, "the planner (conv_plan.h) sizes the slices for this index table");
 
 // TN = 4: 256 x 256 tiles (256 output channels); TN = 2: 256 x 128 tiles (128 output channels: the address unit is busy 62 %
 // of the matrix time instead of 42 % - still the better side of k_conv_dma's 83 % where the map fills the chip in whole rounds)
@@ -244,96 +245,9 @@ __global__ void __launch_bounds__(512, 2) k_conv_wide(ConvArgsH a) {
   h2_store_tile<TM, TN, EMIT>(a, acc, m0, n0, wm, wn, h, l31);
 }
 
-// ph_conv_desc.route (tests/test_hip_wide.py): PH_ROUTE_WIDE_ALWAYS = every served shape whatever its size, PH_ROUTE_WIDE_NEVER = none
-
-template <int TN>
-static int launch_wide(const ConvArgsH &a, hipStream_t st) {
-  constexpr int BN = 2 * TN * 32;
-  ConvArgsH args = a;
-  args.n_row_tiles = (int)((a.n_out + 255) / 256);
-  args.n_col_tiles = (a.cout + BN - 1) / BN;
-  const int ntiles = args.n_row_tiles * args.n_col_tiles;
-  const int grid = ((ntiles + 7) / 8) * 8;
-  const bool emit = args.out_split != nullptr && args.ksplit == 1;
-  if (emit) hipLaunchKernelGGL((k_conv_wide<TN, true>), dim3(grid, 1), dim3(512), 0, st, args);
-  else hipLaunchKernelGGL((k_conv_wide<TN, false>), dim3(grid, args.ksplit), dim3(512), 0, st, args);
-  PH_LAUNCH_CHECK();
-  if (args.ksplit > 1) {
-    if (int rc = ph_launch_splitk_epilogue(args, st)) return rc;
-  }
-  ph_record_cfg(2, 256, BN, 32, args.ksplit, emit ? 1 : 0, 6, 8);
-  return 0;
-}
-
-// Takes gather launches with 256 or 128 output channels and >= 8 kernel offsets; -1 = not served (the caller goes on to
-// k_conv_dma).  One workgroup per CU.  256 channels: maps with at least ~160 row tiles run unsplit (one round); fewer row
-// tiles are split over the kernel offsets so that the launch has about one workgroup per CU, each slice at most WIDE_KMAX
-// offsets.  128 channels: only where the row tiles fill the CUs in (nearly) whole rounds - k_conv_dma's two workgroups per
-// CU and its tail split serve the other sizes better.
-int ph_conv_wide_try(const ConvArgsH &a_in, hipStream_t st) {
-  if ((a_in.cout != 256 && a_in.cout != 128) || a_in.kvol < 8 || a_in.tile_k != nullptr || a_in.win_gather || (a_in.cpad & 31) ||
-      a_in.nbr == nullptr)
-    return -1;
-  const int64_t trow = (a_in.n_out + 255) / 256;
-  // measured (profiles/r3n_layer_ab_wide.txt): 477 vs 520 us at 53 k rows, 162 vs 188 us at 15.6 k rows; below ~12 k rows
-  // (fewer than 48 row tiles: a deep split over the offsets) and on the bottleneck's 245 / 75-offset products k_conv_dma's
-  // smaller tiles win
-  if (a_in.route & PH_ROUTE_WIDE_NEVER) return -1;
-  if (!(a_in.route & PH_ROUTE_WIDE_ALWAYS)) {
-    if (a_in.kvol > WIDE_KMAX) return -1;
-    if (a_in.cout == 256 && trow < 48) return -1;
-    if (a_in.cout == 128) {      // whole rounds only: the last round at least ~60 % full, no split over the offsets
-      const int64_t rest = trow % 256;
-      if (trow >= 256 && rest != 0 && rest < 150 && a_in.ksplit == 1 && a_in.partial == nullptr && a_in.tail_ws != nullptr) {
-        // whole rounds + a few row tiles (the encoder's 71.5 k-row level: 280 tiles): the whole rounds here (0.35 of the matrix peak
-        // against k_conv_dma's 0.24), the left-over rows on k_conv_dma, split over the offsets so that they fill the chip
-        const int64_t r0 = (trow - rest) * 256, tail_rows = a_in.n_out - r0;
-        int ks = (int)(512 / ((tail_rows + 127) / 128));
-        if (ks > a_in.kvol / 3) ks = a_in.kvol / 3;
-        if (ks > 12) ks = 12;
-        while (ks > 1 && (a_in.kvol + (a_in.kvol + ks - 1) / ks - 1) / ((a_in.kvol + ks - 1) / ks) != ks) --ks;      // no empty slice
-        const char *zero0 = ph_dma_zero_line();
-        if (ks >= 2 && zero0 != nullptr && (int64_t)ks * tail_rows * a_in.cout * 4 <= a_in.tail_ws_bytes) {
-          ConvArgsH head = a_in;
-          head.zero = zero0;
-          head.ablate = 0;
-          head.n_out = r0;
-          head.ksplit = 1;
-          head.partial = nullptr;
-          if (int rc = launch_wide<2>(head, st)) return rc;
-          ConvArgsH tail = a_in;
-          tail.n_out = tail_rows;
-          tail.nbr = a_in.nbr + r0;
-          if (tail.out) tail.out = a_in.out + r0 * a_in.cout;
-          if (tail.out_split) tail.out_split = a_in.out_split + r0 * a_in.cout * 2;
-          if (tail.residual) tail.residual = a_in.residual + r0 * a_in.cout;
-          if (tail.axis_coords) tail.axis_coords = a_in.axis_coords + r0 * 4;
-          tail.ksplit = ks;
-          tail.partial = (float *)a_in.tail_ws;
-          return ph_conv_dma_try(tail, 128, st);
-        }
-      }
-      if (trow < 150 || (rest != 0 && rest < 150)) return -1;
-    }
-  }
-  const char *zero = ph_dma_zero_line();
-  if (zero == nullptr) return -1;
-  ConvArgsH a = a_in;
-  a.zero = zero;
-  a.ablate = 0;
-  int ks = (a.kvol + WIDE_KMAX - 1) / WIDE_KMAX;                     // what the index table demands
-  if (trow * ks < 160) {                                             // well under one workgroup per CU: split further
-    int want = (int)((256 + trow / 2) / trow);
-    const int kmax = a.kvol / 3 > 0 ? a.kvol / 3 : 1;
-    if (want > kmax) want = kmax;
-    if (want > ks) ks = want;
-  }
-  a.ksplit = 1;
-  a.partial = nullptr;
-  if (ks > 1) {
-    if (a.tail_ws == nullptr || (int64_t)ks * a.n_out * a.cout * 4 > a.tail_ws_bytes) return -1;
-    a.ksplit = ks;
-    a.partial = (float *)a.tail_ws;
-  }
-  return a.cout == 256 ? launch_wide<4>(a, st) : launch_wide<2>(a, st);
+// 256 x 256 tiles (256 output channels) or 256 x 128 (128); which launches come here, and how they are split: conv_plan.h
+int ph_conv_wide_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st) {
+  const ConvKernelFn k = s.bn == 256 ? (s.emit ? k_conv_wide<4, true> : k_conv_wide<4, false>)
+                                     : (s.emit ? k_conv_wide<2, true> : k_conv_wide<2, false>);
+  return ph_launch_tiles(k, a, s, st);
 }

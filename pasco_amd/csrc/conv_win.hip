@@ -567,47 +567,10 @@ __global__ void __launch_bounds__(WAVES * 64, 2) k_conv_win(ConvArgsH a) {
   h2_store_tile<TM, TN, EMIT>(a, acc, m0, n0, wm, wn, h, l31);
 }
 
-template <int WAVES, int WM, int WN, int TM, int TN, int WMAX>
-static int launch_win(const ConvArgsH &a, hipStream_t st) {
-  constexpr int BN = WN * TN * 32;
-  ConvArgsH args = a;
-  args.n_row_tiles = (int)((a.n_out + WIN_BM - 1) / WIN_BM);
-  args.n_col_tiles = (a.cout + BN - 1) / BN;
-  const int ntiles = args.n_row_tiles * args.n_col_tiles;
-  const int grid = ((ntiles + 7) / 8) * 8;
-  const bool emit = args.out_split != nullptr;
-  if (emit)
-    hipLaunchKernelGGL((k_conv_win<WAVES, WM, WN, TM, TN, WMAX, true>), dim3(grid), dim3(WAVES * 64), 0, st, args);
-  else
-    hipLaunchKernelGGL((k_conv_win<WAVES, WM, WN, TM, TN, WMAX, false>), dim3(grid), dim3(WAVES * 64), 0, st, args);
-  PH_LAUNCH_CHECK();
-  return 0;
-}
-
-// Launches the window kernel (it returns at once on maps the predicate hands to the gather kernel).  bn: 64 or 128.
-int ph_conv_win_launch(const ConvArgsH &a, int bn, hipStream_t st) {
-  ConvArgsH b = a;
-  b.ksplit = 1;
-  b.partial = nullptr;
-  b.zero = ph_dma_zero_line();
-  b.ablate = ph_dma_ablate_bits();
-  if (b.zero == nullptr) {
-    ph_set_error("conv_fwd(windows): no zero line");
-    return 2;
-  }
-  if (bn == 64) {
-    b.win_which = 0 | ph_win_force_bits(b.route);
-    // 64-wide outputs: offset-parallel waves on 16-channel chunks (conv_wop.hip, round 6) when the caller gave the fragment-order
-    // copy of the kernel; else (and PASCO_WOP=0 in the development build) the row-parallel window kernel below
-    static const bool wop2 = [] { const char *e = PH_DEV_ENV("PASCO_WOP"); return e == nullptr || atoi(e) != 0; }();
-    if (wop2 && b.cout <= 64 && b.w_frag != nullptr) {
-      ConvArgsH args = b;
-      args.n_row_tiles = (int)((b.n_out + WIN_BM - 1) / WIN_BM);
-      args.n_col_tiles = 1;
-      return ph_conv_wop2_launch(args, st);
-    }
-    return launch_win<4, 4, 1, 1, 2, WIN_MAX_64>(b, st);
-  }
-  b.win_which = 1 | ph_win_force_bits(b.route);
-  return launch_win<8, 2, 4, 2, 1, WIN_MAX_128>(b, st);
+// The window side of a pair (it returns at once on maps the predicate hands to the gather kernel): 128 x 64 tiles on 4 waves or
+// 128 x 128 on 8.  64-wide outputs with fragment-order weights go to k_conv_wop2 instead (conv_wop.hip) - conv_plan.h decides.
+int ph_conv_win_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st) {
+  const ConvKernelFn k = s.bn == 64 ? (s.emit ? k_conv_win<4, 4, 1, 1, 2, WIN_MAX_64, true> : k_conv_win<4, 4, 1, 1, 2, WIN_MAX_64, false>)
+                                    : (s.emit ? k_conv_win<8, 2, 4, 2, 1, WIN_MAX_128, true> : k_conv_win<8, 2, 4, 2, 1, WIN_MAX_128, false>);
+  return ph_launch_tiles(k, a, s, st);
 }

@@ -469,19 +469,10 @@ __global__ void __launch_bounds__(256, 2) k_conv_wop2(ConvArgsH a) {
 #endif
 }
 
-// Launches the window side of a pair for 64-wide outputs (conv_win.hip: ph_conv_win_launch); needs args.w_frag.
-int ph_conv_wop2_launch(const ConvArgsH &args, hipStream_t st) {
-  const int grid = ((args.n_row_tiles + 7) / 8) * 8;
-  const bool emit = args.out_split != nullptr;
+// The window side of a pair for 64-wide outputs (one column tile: cout <= 64); needs a.w_frag.
+int ph_conv_wop2_launch(const ConvArgsH &a, const ConvStep &s, hipStream_t st) {
 #ifdef PH_DEV
-  if (g_w2_trace_on && !emit) {        // never on a launch that has to write the next layer's operand
-    hipLaunchKernelGGL((k_conv_wop2<false, true>), dim3(grid), dim3(256), 0, st, args);
-    PH_LAUNCH_CHECK();
-    return 0;
-  }
+  if (g_w2_trace_on && !s.emit) return ph_launch_tiles(k_conv_wop2<false, true>, a, s, st);   // never on a launch that writes the next layer's operand
 #endif
-  if (emit) hipLaunchKernelGGL((k_conv_wop2<true>), dim3(grid), dim3(256), 0, st, args);
-  else hipLaunchKernelGGL((k_conv_wop2<false>), dim3(grid), dim3(256), 0, st, args);
-  PH_LAUNCH_CHECK();
-  return 0;
+  return ph_launch_tiles(s.emit ? k_conv_wop2<true> : k_conv_wop2<false>, a, s, st);
 }
