@@ -1,6 +1,6 @@
 """What every ctypes binding of libpascohip.so shares: setting the signatures, the ABI handshake, the error path, the stream
 handle and the process-wide instances.  `me.backend` (ph_*) uses `bind` and `_raw_stream`; the side families (pa_*, pe_*, pf_*, pg_*,
-pl_*, pm_*, pn_*, pr_*, ps_*, pt_*, pv_*, pw_*) derive their binding class from `FamilyLib` and keep only their table and wrappers."""
+pl_*, pm_*, pn_*, po_*, pr_*, ps_*, pt_*, pv_*, pw_*) derive their binding class from `FamilyLib` and keep only their table and wrappers."""
 from __future__ import annotations
 
 import ctypes as C

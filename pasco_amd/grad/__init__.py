@@ -5,7 +5,8 @@ completion losses (include/pasco_semloss.h); and of training-mode batch normalis
 (include/pasco_norm.h: `normlib` binds the `pn_*` entry points, `norm.batch_norm_rows` is the operator).  `host` restates them in torch (CPU tensors, the tensor's dtype), `lib` binds the
 `pg_*` entry points, `rowlib` the `pr_*` ones, `attnlib` the `pa_*` ones, `matchlib` the `pm_*` ones and `semlib` the `ps_*` ones;
 the functions here serve a tensor from the one its device calls for.  The autograd functions that use them are
-`pasco_amd.me.autograd`, `pasco_amd.grad.attention`, `pasco_amd.grad.criterion` and `pasco_amd.grad.semloss`."""
+`pasco_amd.me.autograd`, `pasco_amd.grad.attention`, `pasco_amd.grad.criterion` and `pasco_amd.grad.semloss`.  The step that
+consumes the gradients is `optim.AdamW` (include/pasco_optim.h: `optimlib` binds the `po_*` entry points)."""
 from __future__ import annotations
 
 import torch
@@ -93,3 +94,4 @@ def mask_loss_bwd(logits, tbits, flags, tgt_of_query, coef, t: int):
 from .semloss import (SemComplLossFunction, compute_sem_compl_loss, compute_sem_compl_loss_kitti360,  # noqa: E402,F401
                       sem_compl_loss)
 from .norm import BatchNormRowsFunction, batch_norm_rows, group_gather  # noqa: E402,F401
+from .optim import AdamW, warmup_cosine  # noqa: E402,F401

@@ -1,8 +1,11 @@
 """Torch restatement of include/pasco_grad.h, include/pasco_rowgrad.h, include/pasco_attngrad.h and include/pasco_norm.h for CPU tensors: index
 operations and matrix products in the tensor's dtype.  The
 CPU tests run on it and `pasco_amd.me.autograd` uses it where the features are not on a GPU.  Same results as the kernels up to
-the order of the fp32 sums."""
+the order of the fp32 sums.  The last section restates include/pasco_optim.h (`optim_*`): the optimiser step of
+`pasco_amd.grad.optim.AdamW` on CPU parameters, the same bits as the kernels given the same sum of squares."""
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -459,3 +462,93 @@ def norm_bwd_dx(dy, x, mean_rstd, weight, bias, act: int, slope: float, total_su
     a0, a1 = (total_sums[0] * inv).to(x.dtype), (total_sums[1] * inv).to(x.dtype)
     ws = mean_rstd[1] if weight is None else weight * mean_rstd[1]
     return ws * ((g - a0) - xh * a1)
+
+
+# ---- include/pasco_optim.h --------------------------------------------------------------------------------------------------
+OPTIM_CHUNK = 4096              # PO_CHUNK
+OPTIM_SCALARS = ("decay", "omb1", "b2", "omb2", "bc2sqrt", "eps", "neg_step", "unused")      # po_scalars
+
+
+def _round_f32(x: float) -> float:
+    """The fp64 value rounded once to fp32 (and held in a Python float again)."""
+    return float(torch.tensor(x, dtype=torch.float64).to(torch.float32))
+
+
+def optim_sqnorm(grads) -> torch.Tensor:
+    """po_sqnorm in torch: fp64 [C], per OPTIM_CHUNK consecutive elements of each gradient the sum of its exact fp64 squares
+    (the order inside a chunk is torch's, not the kernel's: the two agree to fp64 rounding)."""
+    parts = []
+    for g in grads:
+        sq = g.reshape(-1).double().square()
+        pad = -sq.numel() % OPTIM_CHUNK
+        if pad:
+            sq = torch.cat([sq, sq.new_zeros(pad)])
+        parts.append(sq.view(-1, OPTIM_CHUNK).sum(dim=1))
+    return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float64)
+
+
+def optim_clip(sumsq: float, max_norm: float, grad_scale: float):
+    """The fp64 expressions of po_prepare: -> (norm, s) with norm = grad_scale * sqrt(sumsq) and the clip scale
+    s = (float)(min(max_norm / (norm + 1e-6), 1) * grad_scale), a NaN staying a NaN; max_norm <= 0 does not clip."""
+    norm = grad_scale * (math.sqrt(sumsq) if sumsq == sumsq and sumsq >= 0 else float("nan"))
+    c = 1.0
+    if max_norm > 0.0:
+        c = max_norm / (norm + 1e-6)
+        if c >= 1.0:
+            c = 1.0
+    return norm, _round_f32(c * grad_scale)
+
+
+def optim_scalars(lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, beta1_pow: float,
+                  beta2_pow: float) -> torch.Tensor:
+    """The fp32 scalars of one tensor's update, fp32 [8] in the order of po_scalars, each formed in fp64 and rounded once;
+    `beta*_pow` are the powers AFTER the step was counted."""
+    bc2 = 1.0 - beta2_pow
+    bc1 = 1.0 - beta1_pow
+    vals = [1.0 - lr * weight_decay, 1.0 - beta1, beta2, 1.0 - beta2, math.sqrt(bc2) if bc2 >= 0 else float("nan"), eps,
+            -lr / bc1 if bc1 != 0 else (float("-inf") if lr > 0 else float("nan")), 0.0]
+    return torch.tensor(vals, dtype=torch.float64).to(torch.float32)
+
+
+def optim_prepare(partials: torch.Tensor, table, hyper, max_norm: float, grad_scale: float, skip: bool, states: torch.Tensor,
+                  scalars: torch.Tensor, result: torch.Tensor, step: torch.Tensor):
+    """po_prepare in torch on host buffers laid out as the header's records: `table` = (group, state index) per tensor,
+    `hyper` = (lr, beta1, beta2, eps, weight_decay) per group, states fp64 [P, 3] (the step an int64 in the first word),
+    scalars fp32 [P, 8], result fp64 [3] (skipped an int64 in the third word), step int32 [2] (the clip an fp32 in the first)."""
+    sumsq = 0.0
+    for x in partials.tolist():
+        sumsq += x
+    finite = sumsq == sumsq and abs(sumsq) != float("inf")
+    apply = finite or not skip
+    norm, s = optim_clip(sumsq, max_norm, grad_scale)
+    result[0], result[1] = sumsq, norm
+    if not apply:
+        result.view(torch.int64)[2] += 1
+    step.view(torch.float32)[0] = s
+    step[1] = int(apply)
+    if not apply:
+        return
+    steps = states.view(torch.int64)
+    for group, i in table:
+        lr, b1, b2, eps, wd = (float(x) for x in hyper[group])
+        steps[i, 0] += 1
+        b1p, b2p = float(states[i, 1]) * b1, float(states[i, 2]) * b2
+        states[i, 1], states[i, 2] = b1p, b2p
+        scalars[i] = optim_scalars(lr, b1, b2, eps, wd, b1p, b2p)
+
+
+def optim_adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s: float, k: torch.Tensor):
+    """po_adamw in torch on one tensor, IN PLACE on p, m, v, in their dtype: `s` the clip scale, `k` the eight scalars.  The
+    order and the grouping are the header's; every torch op below rounds once, so on fp32 these are the kernel's bits."""
+    k = k.to(p.dtype)
+    decay, omb1, b2, omb2, bc2sqrt, eps, neg_step = (k[i] for i in range(7))
+    with torch.no_grad():
+        gs = g * torch.tensor(s, dtype=p.dtype)
+        p.copy_(p * decay)
+        m.copy_(m + (gs - m) * omb1)
+        v.copy_(v * b2 + (gs * gs) * omb2)
+        # the IEEE square root: torch's vectorised fp32 sqrt on the CPU is one ulp off it in ~0.6 % of elements, while the fp64
+        # root rounded to fp32 is the correctly rounded fp32 root (53 >= 2 * 24 + 2 bits: the second rounding is innocuous)
+        root = v.sqrt() if v.dtype == torch.float64 else v.double().sqrt().to(v.dtype)
+        d = root / bc2sqrt + eps
+        p.copy_(p + (m / d) * neg_step)
