@@ -5,7 +5,7 @@
 // times: 80 bytes a row, the second and third pass hit L1), the cross-entropy partials of the row range and, per class, the
 // bits of err = |[y == c] - p_c| as the sort key (a non-negative float orders as its bit pattern).  1 - p_y is formed as the sum
 // of the OTHER exponentials over the sum, never by subtraction.  A workgroup owns one range of rows; k_rows_final adds the
-// ranges in ascending order.
+// ranges in ascending order (the two CE sums in fp64, rounded once).
 //
 // ps_sort_desc: a least-significant-digit radix sort of (key, index) pairs over 8-bit digits of ~key (ascending in ~key =
 // descending in key; LSD passes are stable and the indices start ascending, so equal keys stay in ascending index order).  Per
@@ -182,11 +182,14 @@ __global__ void __launch_bounds__(64) k_rows_final(const float *__restrict__ par
       info[tid - c] = s;
   }
   if (tid == 63) {
-    float num = 0.f, den = 0.f;
+    // the ranges' fp32 partials are folded in fp64 and rounded once: a chain of up to 256 fp32 additions would put its own
+    // error (2e-7 of den at 171 ranges) into every element of the CE gradient, which divides by den
+    double num64 = 0.0, den64 = 0.0;
     for (int64_t r = 0; r < ranges; ++r) {
-      num += part[r * PART_WORDS];
-      den += part[r * PART_WORDS + 1];
+      num64 += (double)part[r * PART_WORDS];
+      den64 += (double)part[r * PART_WORDS + 1];
     }
+    const float num = (float)num64, den = (float)den64;
     ce[0] = num / den;
     ce[1] = num;
     ce[2] = den;

@@ -23,14 +23,51 @@ SHAPES = [
     (100, 30, 257),                                   # the decoder's shape; three row ranges, the last with one row
     (128, 128, 130),                                  # both limits; two ranges
     (3, 2, 0),                                        # no rows
+    # past the first trip: T in 65 .. 96 (three 32-wide target tiles) at both ends and in the middle, each with a partial last
+    # range; as many ranges as there can be; ranges that have grown past their least length
+    (3, 70, 300), (5, 65, 129), (100, 96, 257),
+    (7, 3, 32768),
+    (7, 3, 32769),
 ]
 MULTI = (100, 30, 257)
+LONG_SHAPES = SHAPES[-5:]
+REPEAT_SHAPES = ((33, 33, 63), MULTI, (5, 65, 129), (7, 3, 32769))      # the two-calls-same-bits and workspace test
 PATTERNS = ("partition", "sparse", "several", "all_unknown", "first_range_unknown", "scaled3", "pm80")
 N_CLASSES = 20
 
 assert geometry(257, 100, 30)["ranges"] == 3 and geometry(256, 100, 30)["ranges"] == 2, \
     "257 rows is the smallest count with three ranges"
 assert MULTI[2] % geometry(MULTI[2], MULTI[0], MULTI[1])["range_rows"] != 0, "a partial last range"
+
+
+# !! `launch_class` restates the dispatch of pm_pair_sums (pasco_amd/csrc/match.hip: k_pair_part<TT> on pad32(T) / 32, the rows
+# !! per range and the ranges, the latter two through the binding's `geometry`).  It is used to CHOOSE shapes and to assert, at
+# !! import, that SHAPES reaches the classes below - never to form an expected value: those come from tests/match_ref64.py.
+MIN_RANGE, MAX_RANGES = 128, 256
+
+
+def launch_class(shape):
+    q, t, n = shape
+    g = geometry(n, q, t)
+    return dict(tt=-(-t // 32), ranges=g["ranges"], range_rows=g["range_rows"],
+                partial_last=g["range_rows"] > 0 and n % g["range_rows"] != 0)
+
+
+def _check_shapes():
+    v = {s: launch_class(s) for s in SHAPES}
+    for tt in (1, 2, 3, 4):
+        assert any(x["tt"] == tt for x in v.values()), f"k_pair_part<{tt}> is not launched"
+    three = [x for s, x in v.items() if x["tt"] == 3]
+    assert {s[1] for s, x in v.items() if x["tt"] == 3} == {65, 70, 96}, "pad32(T) / 32 == 3 at both ends and in the middle"
+    assert all(x["partial_last"] and x["ranges"] >= 2 for x in three), "each with a partial last range"
+    assert any(x["ranges"] == MAX_RANGES and x["range_rows"] == MIN_RANGE and not x["partial_last"] for x in v.values()), "ranges == 256"
+    assert any(x["range_rows"] > MIN_RANGE and x["partial_last"] for x in v.values()), "range_rows > 128"
+    assert v[(7, 3, 32769)]["range_rows"] == 160 and v[(7, 3, 32769)]["ranges"] == 205
+    assert all(x["ranges"] <= 3 and x["range_rows"] == MIN_RANGE for s, x in v.items() if s not in LONG_SHAPES and s[2] > 0)
+    assert all(s in SHAPES for s in REPEAT_SHAPES) and LONG_SHAPES[1] in REPEAT_SHAPES and LONG_SHAPES[4] in REPEAT_SHAPES
+
+
+_check_shapes()
 
 
 def pack_words(tgt, known):

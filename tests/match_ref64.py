@@ -19,9 +19,12 @@ M = about twice the worst ratio measured over all cases of tests/match_cases.py 
         (loss_mask, Q31 T1 N65): every ratio above 3 belongs to a tensor of one or two elements        -> PM_M[0] = 5000
         worst over the tensors of >= 64 elements: 2.758 (dlogits at Q7 T3 N70, sparse), then 2.309, 2.071 -> PM_M[1] = 6
         the recorded scenes: losses 2.569, dlogits 1.729, dquery 1.084
+        the long shapes (T = 65, 70, 96: three target tiles; N = 32 768 and 32 769: 256 ranges, ranges of 160 rows):
+        worst 15.114 (loss_dice at Q7 T3 N32769, first_range_unknown: 3 elements), >= 64 elements 2.789 (dlogits, Q100 T96 N257)
     on the CPU (grad/host.py), 234 tensors:
         worst 2441.576 (the same one-element tensor), then 272.442, 91.359                               -> PM_HOST_M[0] = 5000
         worst over the tensors of >= 64 elements: 2.925 (dlogits at Q7 T3 N70, sparse), then 2.298, 2.260 -> PM_HOST_M[1] = 6
+        the long shapes: worst 7.337 (the same 3-element loss_dice), >= 64 elements 2.789 (dlogits, Q100 T96 N257)
 The rule is ill-conditioned on a one-element tensor: a correctly rounded fp32 result can be any multiple of a yardstick that
 happens to be nearly exact.  So each constant is a pair: [0] is the measured bound for every tensor, as above; [1] is a SECOND,
 tighter bound that a tensor of >= WIDE = 64 elements must meet as well (`bound_for`).

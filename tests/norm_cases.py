@@ -21,6 +21,102 @@ CASES = [(n, c, ACT_NAMES[(i + j) % 3]) for i, n in enumerate(ROWS) for j, c in 
 SLOPE, EPS, MOMENTUM = 0.07, 1e-5, 0.1
 MU, S = 0.37, 1.3
 
+# ---- past the first trip of the loops ----------------------------------------------------------------------------------------
+# The tables above stop at 4 tiles and two multiples of 4 among the channel counts.  These reach what a scene runs: records
+# beyond one wave and beyond one pass of the merge kernels, and the vector geometry at the net's widths.
+LONG_ROWS = (9 * T + 1, 32 * T, 32 * T + 1, 65 * T + 3)
+VECTOR_C = (4, 8, 16, 64, 128, 256, 260)     # c % 4 == 0: L = 1, 2, 4, 16, 32, 64 and, at 260, a second block of channel units
+SCALAR_C = (2, 6, 10, 18)                    # c % 4 != 0: L = 2, 8, 16, 32
+# c > 64 is left out at the longest n: the classes it would reach are reached at 32 T + 1 already
+LONG_CASES = [(n, c, ACT_NAMES[(i + j) % 3]) for i, n in enumerate(LONG_ROWS) for j, c in enumerate(VECTOR_C + SCALAR_C)
+              if not (n == LONG_ROWS[-1] and c > 64)]
+MERGE_R = (8, 9, 31, 32, 33, 64, 65, 97)     # records handed to the merge kernels
+MERGE_C = (3, 20)                            # one partial block of MERGE_CH channels; a full one and a partial one
+CHUNK_CYCLE = (0, 1, 3, T, T + 2)            # the rows of record i are CHUNK_CYCLE[i % 5]: unequal counts, empty records
+MISALIGNED_C = (32, 256)
+VIRTUAL_RANKS_C = (65, 128)
+
+BLOCK, MERGE_CH, MERGE_K, WAVE_RECORDS = 256, 8, 32, 8      # csrc/norm.hip: threads, channels and records per pass / per wave
+
+
+# !! `row_geometry` and `merge_geometry` restate the launch arithmetic of pasco_amd/csrc/norm.hip.  They are used to CHOOSE shapes
+# !! and to assert, at import, that the tables above reach every launch class - never to form an expected value: those come
+# !! from tests/norm_ref64.py and from the host restatement alone.
+def row_geometry(n, c, aligned=True):
+    V = 4 if (c % 4 == 0 and aligned) else 1
+    cu, L = c // V, 1
+    while L < cu and L < 64:
+        L *= 2
+    tiles = -(-n // T)
+    return dict(V=V, L=L, R=BLOCK // L, grid_y=-(-cu // L), tiles=tiles, passes=-(-tiles // MERGE_K))
+
+
+def merge_geometry(counts, c):
+    """counts: the rows of every record in order -> which waves and passes hold a non-empty / an empty record."""
+    slots = [(i // MERGE_K, (i % MERGE_K) // WAVE_RECORDS, n > 0) for i, n in enumerate(counts)]
+    return dict(passes=-(-len(counts) // MERGE_K), full_last_pass=len(counts) % MERGE_K == 0,
+                rows_in_upper_waves=any(w > 0 and has for _, w, has in slots),
+                empty_in_upper_waves=any(w > 0 and not has for _, w, has in slots),
+                rows_in_later_pass=any(p > 0 and has for p, _, has in slots),
+                empty_in_later_pass=any(p > 0 and not has for p, _, has in slots),
+                rows_in_upper_waves_of_later_pass=any(p > 0 and w > 0 and has for p, w, has in slots),
+                channel_blocks=-(-c // MERGE_CH), partial_block=c % MERGE_CH != 0)
+
+
+def merge_counts(r):
+    return [CHUNK_CYCLE[i % len(CHUNK_CYCLE)] for i in range(r)]
+
+
+def _check_norm_tables():
+    assert (BLOCK, MERGE_K) == (256, BLOCK // MERGE_CH) and WAVE_RECORDS == 64 // MERGE_CH
+    old = [row_geometry(n, c) for n, c, _ in CASES]
+    assert max(g["tiles"] for g in old) <= WAVE_RECORDS, "the short table stays inside the first wave's records"
+    new = [row_geometry(n, c) for n, c, _ in LONG_CASES]
+    for L in (1, 2, 4, 16, 32, 64):
+        assert any(g["V"] == 4 and g["L"] == L for g in new), f"the vector path at L = {L}"
+    assert any(g["V"] == 4 and g["L"] == 8 for g in old), "the vector path at L = 8 (the short table)"
+    assert any(g["V"] == 4 and g["grid_y"] == 2 for g in new), "the vector path with a second block of channel units"
+    for L in (2, 8, 16, 32):
+        assert any(g["V"] == 1 and g["L"] == L for g in new), f"the scalar path at L = {L}"
+    for c in VECTOR_C + SCALAR_C:
+        mine = [row_geometry(n, k) for n, k, _ in LONG_CASES if k == c]
+        assert any(WAVE_RECORDS < g["tiles"] < MERGE_K for g in mine), f"c = {c}: tile records in waves 1 - 3, one pass"
+        assert any(g["tiles"] == MERGE_K for g in mine), f"c = {c}: exactly one full pass"
+        assert any(g["tiles"] == MERGE_K + 1 for g in mine), f"c = {c}: one record in the second pass"
+        if c <= 64:
+            assert any(g["passes"] == 3 for g in mine), f"c = {c}: three passes"
+    for n in LONG_ROWS:
+        assert sorted({a for k, _, a in LONG_CASES if k == n}) == sorted(ACT_NAMES), f"n = {n} meets every activation"
+    g = row_geometry(T + 1, 256, aligned=False)
+    assert 256 in MISALIGNED_C and (g["V"], g["L"], g["grid_y"]) == (1, 64, 4), "misaligned rows at c = 256: scalar, four blocks"
+    assert row_geometry(3 * T + 5, 128)["L"] == 32 and 128 in VIRTUAL_RANKS_C, "the virtual ranks at L = 32 on the vector path"
+    ms = {(r, c): merge_geometry(merge_counts(r), c) for r in MERGE_R for c in MERGE_C}
+    v = list(ms.values())
+    assert any(m["passes"] == 1 and m["rows_in_upper_waves"] and not m["full_last_pass"] for m in v), "one pass, records in wave 1"
+    assert any(m["passes"] == 1 and m["full_last_pass"] for m in v), "exactly one full pass"
+    assert any(m["passes"] == 1 and m["empty_in_upper_waves"] for m in v), "an empty record inside waves 1 - 3"
+    assert any(m["passes"] == 2 and m["rows_in_later_pass"] and not m["rows_in_upper_waves_of_later_pass"] for m in v), \
+        "a second pass of one wave"
+    assert any(m["passes"] == 2 and m["full_last_pass"] for m in v), "two full passes"
+    assert any(m["passes"] == 2 and m["empty_in_later_pass"] for m in v), "an empty record inside the second pass"
+    assert any(m["passes"] >= 3 and m["rows_in_upper_waves_of_later_pass"] for m in v), "three passes and more"
+    assert ms[(8, 3)]["passes"] == 1 and not ms[(8, 3)]["rows_in_upper_waves"] and ms[(9, 3)]["rows_in_upper_waves"], \
+        "r = 8 ends with wave 0, r = 9 is the first with a record in wave 1"
+    assert any(m["channel_blocks"] == 1 and m["partial_block"] for m in v), "one partial block of MERGE_CH channels"
+    assert any(m["channel_blocks"] == 3 and m["partial_block"] for m in v), "full blocks of MERGE_CH channels and a partial one"
+
+
+_check_norm_tables()
+
+_LONG_WORST = {}
+
+
+def note_long(device, worst: float):
+    """The running worst ratio over the cases of this section, per device, printed with every one of them."""
+    kind = torch.device(device).type
+    _LONG_WORST[kind] = max(_LONG_WORST.get(kind, 0.0), worst)
+    print(f"[norm] long cases on {kind} so far: worst {_LONG_WORST[kind]:.3f}")
+
 
 def ops_of(device):
     """The entry points under test: the binding on a GPU, the restatement on the CPU."""
@@ -141,6 +237,55 @@ def check_split_merge(device):
         perm = torch.stack([recs[i] for i in (2, 0, 3, 1)])
         assert_bound(_moment_ratio(ops.moments_merge(perm), x), f"c = {c}: permuted per-tile records")
         assert_bound(_moment_ratio(whole, x), f"c = {c}: the whole")
+
+
+def check_split_merge_long(device, n):
+    """The same identity where the fold leaves the first wave's records and the first pass: whole == merge of the per-tile
+    records, bit for bit, with and without empty records in between."""
+    ops, tile = ops_of(device), tile_rows_of(device)
+    for c in (20, 283):
+        x = inputs(n, c, device)[0]
+        whole = ops.moments(x)
+        assert float(whole[0].min()) == float(whole[0].max()) == n
+        recs = [ops.moments(x[r0:r0 + tile].contiguous()) for r0 in range(0, n, tile)]
+        assert len(recs) == row_geometry(n, c)["tiles"] > WAVE_RECORDS
+        assert torch.equal(ops.moments_merge(torch.stack(recs)), whole), f"n = {n}, c = {c}: per-tile records"
+        empty = ops.moments(x[:0].contiguous())
+        spread = [t for i, rec in enumerate(recs) for t in ((empty, rec) if i % 7 == 3 else (rec,))]
+        assert len(spread) > len(recs)
+        assert torch.equal(ops.moments_merge(torch.stack(spread)), whole), f"n = {n}, c = {c}: with empty records in between"
+        r = _moment_ratio(whole, x)
+        assert_bound(r, f"n = {n}, c = {c}: the whole")
+        note_long(device, max(r.values()))
+
+
+def check_merge_records(device, r, c):
+    """`r` records of unequal and empty row chunks (CHUNK_CYCLE) of one x through the two merge entry points.  Both sides of the
+    family evaluate w = n_b / (n + n_b), mean + d * w and (m2 + q) + (d * d) * (n * w) in fp64 in ascending order with
+    contraction off, so the result equals the host restatement's bit for bit; the merged moments are also held to the accuracy
+    bound against fp64 over the concatenated rows."""
+    ops = ops_of(device)
+    counts = merge_counts(r)
+    n = sum(counts)
+    x, dy, w, b, _, _ = inputs(n, c, device)
+    cuts = [sum(counts[:i]) for i in range(r + 1)]
+    xs = [x[a:z].contiguous() for a, z in zip(cuts[:-1], cuts[1:])]
+    dys = [dy[a:z].contiguous() for a, z in zip(cuts[:-1], cuts[1:])]
+    recs = torch.stack([ops.moments(t) for t in xs])
+    assert recs[:, 0, 0].tolist() == [float(k) for k in counts]
+    got = ops.moments_merge(recs)
+    want = host.norm_moments_merge(recs.cpu())
+    assert torch.equal(got.cpu().view(torch.int64), want.view(torch.int64)), \
+        f"r = {r}, c = {c}: moments_merge differs from the restatement in {int((got.cpu() != want).sum())} of {want.numel()} values"
+    ratio = _moment_ratio(got, x)
+    assert_bound(ratio, f"r = {r}, c = {c}: merged records of unequal chunks")
+    note_long(device, max(ratio.values()))
+    mean_rstd = ops.finish(got, EPS, 0.0, None, None)
+    sums = torch.stack([ops.bwd_sums(d, t, mean_rstd, w, b, host.ACT_LEAKY, SLOPE) for t, d in zip(xs, dys)])
+    got = ops.sums_merge(sums)
+    want = host.norm_sums_merge(sums.cpu())
+    assert torch.equal(got.cpu().view(torch.int64), want.view(torch.int64)), \
+        f"r = {r}, c = {c}: sums_merge differs from the restatement in {int((got.cpu() != want).sum())} of {want.numel()} values"
 
 
 # ---- edges -------------------------------------------------------------------------------------------------------------------
@@ -273,11 +418,22 @@ def check_virtual_ranks(device, act="relu", c=65):
     return r
 
 
-def check_misaligned(device):
-    """c % 4 == 0 with x and dy 4 bytes past a 16-byte boundary: the kernels fall back to 4-byte accesses."""
+def check_misaligned(device, c=32):
+    """c % 4 == 0 with x and dy 4 bytes past a 16-byte boundary: the kernels fall back to 4-byte accesses (at c = 256 with 64
+    lanes along a row and four blocks of channels)."""
     from tests.grad_cases import misaligned
-    n, c = T + 1, 32
+    assert c in MISALIGNED_C
+    n = T + 1
     x, dy, w, b, rm, rv = inputs(n, c, device)
     xm, dym = misaligned(x), misaligned(dy)
     got, _ = run_op([xm], [dym], w, b, rm, rv, "relu")
-    assert_bound(ratios(got, *twins([x], [dy], w, b, rm, rv, "relu")), "misaligned rows")
+    r = ratios(got, *twins([x], [dy], w, b, rm, rv, "relu"))
+    assert_bound(r, f"misaligned rows, c = {c}")
+    return r
+
+
+def check_long_case(device, n, c, act):
+    """One of LONG_CASES through `check_case`, its worst ratio noted."""
+    assert (n, c, act) in LONG_CASES
+    r = check_case(device, n, c, act)
+    note_long(device, max(r.values()))

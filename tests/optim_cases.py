@@ -43,15 +43,82 @@ def case_values(n_steps: int = 3, seed: int = 0):
 GROUPS = ([0, 2, 4, 6, 8], DECAY), ([1, 3, 5, 7], NO_DECAY)      # indices into the case's tensors
 
 
-def make_params(values, device):
+# ---- past the first trip of the loops ----------------------------------------------------------------------------------------
+# The case above is 9 tensors and 14 chunks: no workgroup of k_sqnorm / k_adamw takes a second chunk and neither loop of
+# k_prepare a second trip.  A net is thousands of tensors and of chunks.
+MAX_GRID, BLOCK = 2048, 256                  # csrc/optim.hip: the grid cap of the table kernels, the threads of a workgroup
+
+
+class LongCase:
+    """sizes: the elements of every tensor; even tensors decay, odd ones do not; `n_steps` steps with the clip acting."""
+
+    def __init__(self, name, sizes, n_steps, seed):
+        self.name, self.sizes, self.n_steps, self.seed = name, tuple(sizes), n_steps, seed
+        self.groups = tuple((idx, wd) for idx, wd in ((list(range(0, len(sizes), 2)), DECAY), (list(range(1, len(sizes), 2)), NO_DECAY))
+                            if idx)
+        self._values = None
+
+    def values(self):
+        """-> (initial parameter values, [(lr, gradient values)] per step) on the host, made once and never written to."""
+        if self._values is None:
+            g = torch.Generator().manual_seed(self.seed)
+            total = sum(self.sizes)
+            flat = torch.randn(total, generator=g)
+            scale = torch.repeat_interleave(torch.tensor([0.03 * (1 + i % 4) for i in range(len(self.sizes))]), torch.tensor(self.sizes))
+            grads = [torch.randn(total, generator=g) * scale for _ in range(self.n_steps)]
+            split = lambda t: [x.clone() for x in t.split(self.sizes)]
+            self._values = split(flat), [(lr, split(gr)) for lr, gr in zip(LRS, grads)]
+        return self._values
+
+
+LONG_CASES = {c.name: c for c in (
+    LongCase("many_tensors", [1 + i % 9 for i in range(2100)] + [3 * PO_CHUNK + 5], 2, 21),
+    LongCase("one_long_tensor", [2049 * PO_CHUNK + 3], 1, 22),
+)}
+
+
+# !! `table_geometry` restates the launch arithmetic of pasco_amd/csrc/optim.hip over the chunk table the optimiser uploads (its
+# !! tensors group by group).  It is used to CHOOSE the sizes and to assert, at import, that the cases reach the classes below -
+# !! never to form an expected value: those come from tests/optim_ref64.py, math.fsum and the host restatement.
+def table_geometry(case: LongCase):
+    order = [i for idx, _ in case.groups for i in idx]
+    tensor_of = [i for i in order for _ in range(-(-case.sizes[i] // PO_CHUNK))]
+    C, T = len(tensor_of), len(order)
+    grid = min(C, MAX_GRID)
+    second = [(tensor_of[b], tensor_of[b + grid]) for b in range(grid) if b + grid < C]
+    last = case.sizes[tensor_of[-1]] % PO_CHUNK
+    return dict(T=T, C=C, grid=grid, second_trips=len(second), changes_tensor=sum(1 for a, b in second if a != b),
+                keeps_tensor=sum(1 for a, b in second if a == b), partial_trips=-(-C // BLOCK), tensor_trips=-(-T // BLOCK),
+                last_chunk=last or PO_CHUNK)
+
+
+def _check_long_cases():
+    small = [(n,) for n in SIZES] + [OFFSET_SHAPE]
+    assert sum(-(-math.prod(s) // PO_CHUNK) for s in small) < MAX_GRID and len(small) < BLOCK, "the short case: one trip everywhere"
+    g = table_geometry(LONG_CASES["many_tensors"])
+    assert (g["T"], g["C"]) == (2101, 2104) and g["grid"] == MAX_GRID
+    assert g["second_trips"] == g["changes_tensor"] == 56, "a workgroup changes its tensor between two trips"
+    assert g["partial_trips"] > 1 and g["tensor_trips"] > 1, "k_prepare: both loops take several trips"
+    assert len(LONG_CASES["many_tensors"].groups) == 2 and LONG_CASES["many_tensors"].n_steps == 2
+    g = table_geometry(LONG_CASES["one_long_tensor"])
+    assert (g["T"], g["C"]) == (1, 2050) and g["second_trips"] == g["keeps_tensor"] == 2, "a second trip that changes the chunk alone"
+    assert g["last_chunk"] == 3, "the last chunk is ragged"
+
+
+_check_long_cases()
+
+
+def make_params(values, device, offset_last: bool = True):
+    if not offset_last:
+        return [torch.nn.Parameter(v.to(device).clone()) for v in values]
     ps = [torch.nn.Parameter(v.to(device).clone()) for v in values[:-1]]
     ps.append(torch.nn.Parameter(offset_view(values[-1].to(device))))
     assert ps[-1].storage_offset() == 1 and ps[-1].data_ptr() % 16 == 4
     return ps
 
 
-def make_optimizer(ps, **kw):
-    return AdamW([{"params": [ps[i] for i in idx], "weight_decay": wd} for idx, wd in GROUPS], lr=LRS[0], betas=BETAS, eps=EPS, **kw)
+def make_optimizer(ps, groups=GROUPS, **kw):
+    return AdamW([{"params": [ps[i] for i in idx], "weight_decay": wd} for idx, wd in groups], lr=LRS[0], betas=BETAS, eps=EPS, **kw)
 
 
 def set_grads(ps, grads, device, offset_last: bool = True):
@@ -85,14 +152,17 @@ def our_records(ps, opt):
     return opt._buffers().get_states()[slots(ps, opt)]
 
 
-def our_run(values, steps, device, **kw):
-    """steps: (lr, grads) per step -> (parameters, optimiser) after the last."""
-    ps = make_params(values, device)
-    opt = make_optimizer(ps, **kw)
+def our_run(values, steps, device, groups=GROUPS, offset_last: bool = True, sums=None, **kw):
+    """steps: (lr, grads) per step -> (parameters, optimiser) after the last; the sum of squares of every step is appended to
+    `sums` where a list is given."""
+    ps = make_params(values, device, offset_last)
+    opt = make_optimizer(ps, groups, **kw)
     for lr, grads in steps:
         set_lr(opt, lr)
-        set_grads(ps, grads, device)
+        set_grads(ps, grads, device, offset_last)
         opt.step()
+        if sums is not None:
+            sums.append(float(opt.sum_of_squares))
     return ps, opt
 
 
@@ -107,10 +177,10 @@ def assert_within(got, v32, v64, what):
     assert not bad, f"{what}: ratio over OPT_M = {ref.OPT_M}: {bad}"
 
 
-def twins(values, steps, max_norm, device):
+def twins(values, steps, max_norm, device, groups=GROUPS):
     """-> (v32 on `device`, v64 on the host)."""
-    v32 = ref.twin_run([v.to(device) for v in values], GROUPS, BETAS, EPS, steps, max_norm, torch.float32)
-    v64 = ref.twin_run(values, GROUPS, BETAS, EPS, steps, max_norm, torch.float64)
+    v32 = ref.twin_run([v.to(device) for v in values], groups, BETAS, EPS, steps, max_norm, torch.float32)
+    v64 = ref.twin_run(values, groups, BETAS, EPS, steps, max_norm, torch.float64)
     return v32, v64
 
 
@@ -345,14 +415,14 @@ def check_scheduler_drives_it(device):
     assert p.grad is None
 
 
-def restate_steps(values, steps, max_norm, sums):
+def restate_steps(values, steps, max_norm, sums, groups=GROUPS):
     """The steps again on the host with the restatement of pasco_amd/grad/host.py: `sums[k]` is the sum of squares the device
     found at step k (read from its result record), from which the clip scale is formed by the same fp64 expression; the
     powers of beta by the same repeated fp64 products.  -> {"p", "m", "v"} on the host."""
     ps = [v.clone() for v in values]
     ms, vs = [torch.zeros_like(v) for v in values], [torch.zeros_like(v) for v in values]
     pows = [[1.0, 1.0] for _ in values]
-    wd = {i: w for idx, w in GROUPS for i in idx}
+    wd = {i: w for idx, w in groups for i in idx}
     for (lr, gs), sumsq in zip(steps, sums):
         _, s = host.optim_clip(sumsq, 0.0 if max_norm is None else max_norm, 1.0)
         for i, g in enumerate(gs):
@@ -363,3 +433,27 @@ def restate_steps(values, steps, max_norm, sums):
             k = host.optim_scalars(lr, BETAS[0], BETAS[1], EPS, wd[i], pows[i][0], pows[i][1])
             host.optim_adamw_(ps[i], g, ms[i], vs[i], s, k)
     return {"p": ps, "m": ms, "v": vs}
+
+
+def check_long(device, name):
+    """A LONG_CASE: its steps against the twins, the first step's sum of squares against math.fsum, a repeat run bit for bit.
+    -> (case, parameters, optimiser, the sums of squares per step) for what the GPU side adds."""
+    case = LONG_CASES[name]
+    values, steps = case.values()
+    sums = []
+    ps, opt = our_run(values, steps, device, case.groups, False, sums, max_norm=CLIP)
+    again = our_run(values, steps, device, case.groups, False, max_norm=CLIP)
+    a, b = our_state(ps, opt), our_state(*again)
+    assert all(bits_equal(a[k], b[k]) for k in ref.QUANTITIES), f"{name}: a repeat run gives other bits"
+    assert torch.equal(opt._buffers().result.view(torch.int64), again[1]._buffers().result.view(torch.int64))
+    assert opt._buffers().get_states().tobytes() == again[1]._buffers().get_states().tobytes()
+    assert our_records(ps, opt)["step"].tolist() == [case.n_steps] * len(ps)
+    assert float(opt.grad_norm) > CLIP, "the clip is meant to act"
+    n = sum(case.sizes)
+    exact = ref.exact_sum_of_squares(steps[0][1])
+    rel = abs(sums[0] - exact) / exact
+    print(f"[optim] {name}: sum of squares over {n} elements: relative error {rel:.3e}, bound {n * 2.0 ** -53:.3e}")
+    assert rel <= n * 2.0 ** -53
+    v32, v64 = twins(values, steps, CLIP, device, case.groups)
+    assert_within(a, v32, v64, f"{name}, {case.n_steps} steps, {device}")
+    return case, ps, opt, sums

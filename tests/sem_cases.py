@@ -13,6 +13,38 @@ SHAPES = [(1, 2), (2, 19), (63, 20), (64, 32), (65, 2), (T - 1, 20), (T, 19), (T
 PATTERNS = ["random", "saturated", "single_class", "all_present", "ignore10", "all_ignore", "outside", "ties"]
 assert semlib.geometry(3 * T + 1, 20)["ranges"] > 1 and semlib.geometry(T, 19)["ranges"] > 1
 
+# Past the first trip: above 65 536 rows a range of k_rows_part is longer than a workgroup, so a thread carries its num and den
+# over two and three rows, and the sort and the Lovasz scan see 33 and 65 tiles.  Appended, so that the shapes above keep their
+# seeds and scales.  Four patterns only; C = 2 with `ties` is left out on purpose: at this size the fp32 yardstick of loss_c
+# is exactly 0 there, so the ratio is infinite for any fp32 route.
+LONG_SHAPES = [(65537, 3), (131077, 3)]
+LONG_PATTERNS = ["random", "ignore10", "ties", "outside"]
+SHAPES += LONG_SHAPES
+# every (shape, pattern) the two legs run, in the order and under the ids the full product had
+CASES = [(s, p) for p in PATTERNS for s in SHAPES if s not in LONG_SHAPES or p in LONG_PATTERNS]
+CASE_IDS = ["N%d_C%d-%s" % (s + (p,)) for s, p in CASES]
+ROWS_BLOCK = 256                 # csrc/semloss.hip: the threads of a workgroup of k_rows_part
+
+
+# !! `launch_class` restates, through the binding's `geometry`, how ps_rows_fwd, ps_sort_desc and ps_lovasz_fwd split N rows.  It
+# !! is used to CHOOSE shapes and to assert, at import, that SHAPES reaches the classes below - never to form an expected value.
+def launch_class(n, c):
+    g = semlib.geometry(n, c)
+    return dict(rows_per_thread=g["range_rows"] // ROWS_BLOCK, tiles=g["tiles"], ranges=g["ranges"])
+
+
+def _check_shapes():
+    short = [launch_class(*s) for s in SHAPES if s not in LONG_SHAPES]
+    assert all(x["rows_per_thread"] == 1 and x["tiles"] <= 4 for x in short), "the short shapes: one row per thread, four tiles"
+    a, b = (launch_class(*s) for s in LONG_SHAPES)
+    assert (a["rows_per_thread"], a["tiles"]) == (2, 33), "two rows per thread of k_rows_part, 33 tiles"
+    assert (b["rows_per_thread"], b["tiles"]) == (3, 65), "three rows per thread of k_rows_part, 65 tiles"
+    assert all(s[0] % (launch_class(*s)["rows_per_thread"] * ROWS_BLOCK) != 0 for s in LONG_SHAPES), "a partial last range"
+    assert all((s, p) in CASES for s in LONG_SHAPES for p in LONG_PATTERNS) and len(CASES) == 9 * 8 + 2 * 4
+
+
+_check_shapes()
+
 
 def scale_of(shape, pattern):
     return (1, 2, 4)[(SHAPES.index(shape) + PATTERNS.index(pattern)) % 3]

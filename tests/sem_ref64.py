@@ -19,10 +19,14 @@ M = about twice the worst ratio measured over all cases of tests/sem_cases.py an
         C32): every ratio above 3 belongs to a tensor of at most 32 elements                              -> PS_M[0] = 1500
         worst over the tensors of >= 64 elements: 2.910 (recorded scene a, the CE gradient at scale 1), then 2.853 (err at N64
         C32 single_class), 2.634, 2.611 (dlogits/lovasz at N64 C32 outside)                                -> PS_M[1] = 6
+        the long shapes (N = 65 537 and 131 077 at C = 3: two and three rows per thread of k_rows_part, 33 and 65 tiles; four
+        patterns): worst 23.589 (lovasz, N131077 random: one element), >= 64 elements 1.396 (err, N131077 random).  Before
+        k_rows_final folded the ranges' CE partials in fp64 the CE gradient at N131077 ties stood at 6.275: over PS_M[1].
     on the CPU (grad/host.py), 696 tensors:
         worst 750.061 (the same one-element tensor), then 93.696 (lovasz, N65 C2 ignore10), 51.592         -> PS_HOST_M[0] = 1500
         worst over the tensors of >= 64 elements: 4.392 (dlogits/ce at N2047 C20 ties), then 3.190 (err at N63 C20
         single_class), 2.515                                                                               -> PS_HOST_M[1] = 9
+        the long shapes: worst 80.540 (ce, N131077 random: one element), >= 64 elements 1.396 (err, N131077 random)
     the recorded scenes' fp32 losses lie within 8.9e-08 relative of this module's fp64 values (the bound is 2^-16).
 The rule is ill-conditioned on a tensor of a few elements: a correctly rounded fp32 result can be any multiple of a yardstick
 that happens to be nearly exact.  So each constant is a pair: [0] is the measured bound for every tensor; [1] is a SECOND, tighter

@@ -217,12 +217,65 @@ def cases():
     return _CASES
 
 
+# ---- past the first trip of the capped grids --------------------------------------------------------------------------------
+# Every case above is at most 64 x 64 x 16 voxels = 256 workgroups, so no grid-stride loop of csrc/target.hip has taken a
+# second trip.  These are kept out of `cases()` and its size assertion, in a list with its own.
+MAX_BLOCKS, BLOCK, WAVES = 2048, 256, 4          # csrc/target.hip: the grid cap, the threads and the waves of a workgroup
+LONG_GRID = (128, 128, 36)
+LONG_FLAT = 4 * (MAX_BLOCKS * BLOCK + 257)       # voxels of the synthetic pt_masks / pt_presence arrays: a multiple of 4
+
+
+# !! `trips` restates the grid arithmetic of pasco_amd/csrc/target.hip (`grid_for`, and k_labels' one wave per 4^3 block).  It
+# !! is used to CHOOSE sizes and to assert that the long cases reach a second trip of every capped grid - never to form an
+# !! expected value: those are the host restatement's and numpy's.
+def trips(work: int, per_block: int = BLOCK) -> int:
+    blocks = min(max(-(-work // per_block), 1), MAX_BLOCKS)
+    return -(-work // (blocks * per_block))
+
+
+def build_long_cases():
+    KI = SK.SEMANTIC_KITTI_THING_IDS
+    turn = lattice_T(flip_y=True, quarter_turns=1, shift_voxels=(3.0, -2.0, 1.0))          # `turn` of build_cases
+    sem, ins = _scene(LONG_GRID, 7)
+    # The crop keeps 0.8 of the scene in x and y, which takes k_labels back under its cap: the second trip of k_labels is the
+    # uncropped case's, the second trip of k_crop_bounds (over the sample box, which no crop shrinks) the cropped one's.
+    return [Case("second_trip", sem, ins, [lattice_T(), turn], None, KI, 20, True),
+            Case("second_trip_crop", sem, ins, [turn], np.array([[0.3, 0.6, 0.1]]), KI, 20, True)]
+
+
+_LONG_CASES = None
+
+
+def long_cases():
+    """The long cases, built, held to `assert_tie_free` and to their launch classes once."""
+    global _LONG_CASES
+    if _LONG_CASES is None:
+        _LONG_CASES = build_long_cases()
+        assert_tie_free(_LONG_CASES[0])             # the second case has the same grid and one of the same transforms
+        for c in _LONG_CASES:
+            assert c.sem.shape == LONG_GRID and trips(c.sem.size) > 1, "k_box, k_samples, k_crop_bounds: a second trip"
+            assert trips(LONG_FLAT // 4) > 1 >= trips(c.sem.size // 4), "k_masks takes its second trip on the synthetic arrays alone"
+        for h in host_targets(_LONG_CASES[0]):
+            scene = tuple(h["semantic_label"].shape)
+            assert trips(scene[0] * scene[1] * scene[2] // 64, WAVES) > 1, f"k_labels: a second trip (scene {scene})"
+            assert trips(scene[0] * scene[1] * scene[2]) > 1, "k_presence: a second trip"
+        h = host_targets(_LONG_CASES[1])[0]
+        assert h["semantic_label"].numel() < host_targets(_LONG_CASES[0])[1]["semantic_label"].numel(), "the crop acts"
+    return _LONG_CASES
+
+
+def long_case_names():
+    return ["second_trip", "second_trip_crop"]
+
+
 def case_names():
     return ["fixture_a", "fixture_b", "fixture_c", "m3", "m3_crop", "no_instances", "no_instances_crop", "instance_ids_zero_only",
             "single_known_voxel", "negative_box", "scene_size_8", "kitti360_classes", "many_targets"]
 
 
 def case(name: str) -> Case:
+    if name in long_case_names():
+        return {c.name: c for c in long_cases()}[name]
     return {c.name: c for c in cases()}[name]
 
 

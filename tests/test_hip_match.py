@@ -79,11 +79,11 @@ def test_hip_target_pack_equals_a_numpy_gather(dev, t, with_unknown, n_outside):
     mc.check_target_pack(dev, t, with_unknown, n_outside)
 
 
-@pytest.mark.parametrize("shape", [(33, 33, 63), mc.MULTI], ids=["one_range", "multi_range"])
+@pytest.mark.parametrize("shape", mc.REPEAT_SHAPES, ids=["one_range", "multi_range", "three_target_tiles", "grown_ranges"])
 def test_hip_two_calls_return_the_same_bits_within_the_declared_workspace(lib, dev, shape):
     from pasco_amd.grad.matchlib import geometry
     Q, T, N = shape
-    assert geometry(N, Q, T)["ranges"] == lib.ranges(N, Q, T) == (1 if shape != mc.MULTI else 3)
+    assert geometry(N, Q, T)["ranges"] == lib.ranges(N, Q, T) == {(33, 33, 63): 1, mc.MULTI: 3, (5, 65, 129): 2, (7, 3, 32769): 205}[shape]
     x = mc.inputs(shape, "sparse")
     logits, tbits, flags = x.logits.to(dev), x.tbits.to(dev), x.flags.to(dev)
     for bit in (0, 1):

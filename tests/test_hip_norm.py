@@ -1,7 +1,7 @@
 """Training-mode batch normalisation over rows on the GPU: the pn_* kernels of libpascohip.so (include/pasco_norm.h) through
 `pasco_amd.grad.norm.batch_norm_rows`, and the module route `set_me_norm("device")`.  The checks are tests/norm_cases.py (shared
 with tests/test_norm_cpu.py), the references tests/norm_ref64.py: the fp64 torch twin, and torch's own fp32 batch_norm on the same
-GPU as the yardstick of the error.  Every case is a few hundred rows."""
+GPU as the yardstick of the error.  The cases of the short table are a few hundred rows; the long ones reach 65 tiles."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -99,6 +99,31 @@ def test_non_fp32_raises(dev):
 @pytest.mark.parametrize("act", nc.ACT_NAMES)
 def test_virtual_ranks(dev, act):
     nc.check_virtual_ranks(dev, act)
+
+
+@pytest.mark.parametrize("n,c,act", nc.LONG_CASES, ids=[f"{n}x{c}_{a}" for n, c, a in nc.LONG_CASES])
+def test_long_case_against_the_fp64_twin(dev, n, c, act):
+    """Tile records beyond the first wave and the first pass of the combine; the vector geometry at the net's widths."""
+    nc.check_long_case(dev, n, c, act)
+
+
+@pytest.mark.parametrize("c", nc.MERGE_C)
+@pytest.mark.parametrize("r", nc.MERGE_R)
+def test_merge_of_unequal_records_equals_the_restatement(dev, r, c):
+    nc.check_merge_records(dev, r, c)
+
+
+@pytest.mark.parametrize("n", nc.LONG_ROWS)
+def test_merge_of_many_tile_records_is_the_whole(dev, n):
+    nc.check_split_merge_long(dev, n)
+
+
+def test_virtual_ranks_at_128_channels(dev):
+    nc.note_long(dev, max(nc.check_virtual_ranks(dev, "relu", c=128).values()))
+
+
+def test_misaligned_rows_at_256_channels(dev):
+    nc.note_long(dev, max(nc.check_misaligned(dev, c=256).values()))
 
 
 def test_restatement_has_the_kernels_records(dev):

@@ -1,7 +1,7 @@
 """`pasco_amd.grad.optim.AdamW` on the GPU: the po_* kernels of libpascohip.so (include/pasco_optim.h).  The checks are
 tests/optim_cases.py (shared with tests/test_optim_cpu.py), the references tests/optim_ref64.py: the fp64 torch twin, torch's
 own fp32 clip + AdamW on the same GPU as the yardstick of the error, and the host restatement, which the update has to equal
-bit for bit.  Every case is nine tensors and a dozen chunks."""
+bit for bit.  The short case is nine tensors and a dozen chunks; the two long ones pass the grid cap of the table kernels."""
 import os
 import re
 
@@ -111,6 +111,40 @@ def test_update_equals_the_restatement_bit_for_bit(dev, max_norm):
         assert (records["beta1_pow"][i], records["beta2_pow"][i]) == (b1p, b2p)
         k = host.optim_scalars(oc.LRS[2], oc.BETAS[0], oc.BETAS[1], oc.EPS, wd[i], b1p, b2p)
         assert torch.equal(scalars[at].view(torch.int32), k.view(torch.int32)), (i, scalars[at].tolist(), k.tolist())
+
+
+@pytest.mark.parametrize("name", list(oc.LONG_CASES))
+def test_more_chunks_than_the_grid_and_more_tensors_than_a_workgroup(dev, name):
+    """The cases of tests/optim_cases.py in which a workgroup of k_sqnorm / k_adamw takes a second chunk (of another tensor, or
+    of the same one) and both loops of k_prepare take several trips: the checks of the shared table, then p, m, v, the state
+    records and the fp32 scalars against the host restatement, bit for bit, under the case's own groups."""
+    case, ps, opt, sums = oc.check_long(dev, name)
+    values, steps = case.values()
+    for sumsq in sums[-1:]:
+        norm, s = host.optim_clip(sumsq, oc.CLIP, 1.0)
+        assert float(opt.grad_norm) == norm and float(opt._buffers().step.view(torch.float32)[0]) == s
+    want = oc.restate_steps(values, steps, oc.CLIP, sums, case.groups)
+    got = oc.our_state(ps, opt)
+    report = []
+    for k in ref.QUANTITIES:
+        for i, (a, b) in enumerate(zip(got[k], want[k])):
+            diff = int((a.cpu().view(torch.int32) != b.view(torch.int32)).sum())
+            if diff:
+                report.append(f"{k} of tensor {i} ({a.numel()} elements): {diff} differ, max {float((a.cpu() - b).abs().max()):.3e}")
+    print(f"[optim] {name}: kernel against restatement: {len(report)} of {3 * len(ps)} tensors differ")
+    assert not report, "\n".join(report[:20])
+    records = oc.our_records(ps, opt)
+    b1p, b2p = 1.0, 1.0
+    for _ in range(case.n_steps):
+        b1p, b2p = b1p * oc.BETAS[0], b2p * oc.BETAS[1]
+    assert records["step"].tolist() == [case.n_steps] * len(ps)
+    assert set(records["beta1_pow"].tolist()) == {b1p} and set(records["beta2_pow"].tolist()) == {b2p}
+    wd = {i: w for idx, w in case.groups for i in idx}
+    scalars = opt._buffers().scalars.cpu().view(torch.int32)
+    lr = steps[-1][0]
+    k_of = {w: host.optim_scalars(lr, oc.BETAS[0], oc.BETAS[1], oc.EPS, w, b1p, b2p).view(torch.int32) for w in set(wd.values())}
+    for i, at in enumerate(oc.slots(ps, opt)):
+        assert torch.equal(scalars[at], k_of[wd[i]]), (i, scalars[at].tolist(), k_of[wd[i]].tolist())
 
 
 def test_first_gradient_at_the_third_step(dev):

@@ -29,8 +29,7 @@ def dev(hip):
     return torch.device("cuda", 0)
 
 
-@pytest.mark.parametrize("pattern", sc.PATTERNS)
-@pytest.mark.parametrize("shape", sc.SHAPES, ids=lambda s: "N%d_C%d" % s)
+@pytest.mark.parametrize("shape,pattern", sc.CASES, ids=sc.CASE_IDS)
 def test_hip_stages_values_and_gradients_against_fp64(hip, shape, pattern):
     sc.check_case("hip", sref.PS_M, shape, pattern)
 
@@ -41,7 +40,7 @@ def test_hip_sort_is_numpys_stable_descending_order(lib, dev, kind, s):
     """No tolerance: a broken histogram, scan, rank or scatter cannot pass.  The scratch has exactly the declared bytes and a
     canary behind it; perm has a canary too."""
     T = sc.T
-    for m in (1, 2, 63, 64, 65, 511, 513, T - 1, T, T + 1, 3 * T + 1):
+    for m in (1, 2, 63, 64, 65, 511, 513, T - 1, T, T + 1, 3 * T + 1) + ((sc.LONG_SHAPES[0][0],) if s == 3 else ()):      # 33 tiles
         keys = cpu.sort_keys(kind, s, m)
         need = lib.sort_workspace_bytes(s, m)
         ws = torch.full((need + GUARD,), 0x5A, dtype=torch.uint8, device=dev)
@@ -105,10 +104,10 @@ def _forward_raw(lib, dev, case, ws_short=0, c_arg=None):
     return {k: v.cpu() for k, v in outs.items()}, rcs
 
 
-@pytest.mark.parametrize("shape", [(65, 20), (3 * sc.T + 1, 20)], ids=lambda s: "N%d_C%d" % s)
+@pytest.mark.parametrize("shape", [(65, 20), (3 * sc.T + 1, 20), sc.LONG_SHAPES[0]], ids=lambda s: "N%d_C%d" % s)
 def test_hip_declared_workspace_canary_and_repeatability(lib, dev, shape):
-    """Exactly the declared bytes are enough, nothing is written behind them, and two calls give the same bits: one range and
-    several."""
+    """Exactly the declared bytes are enough, nothing is written behind them, and two calls give the same bits: one range,
+    several, and ranges of two rows per thread over 33 tiles."""
     case = sc.make_case(shape, "ignore10", scale=2)
     a, rcs = _forward_raw(lib, dev, case)
     assert rcs == [0, 0, 0, 0], lib.lib.ps_last_error()

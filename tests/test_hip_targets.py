@@ -31,7 +31,7 @@ def assert_same(got, want, what):
     assert torch.equal(got, want), f"{what}: {int((got != want).sum())} of {want.numel()} values differ"
 
 
-@pytest.mark.parametrize("name", tc.case_names())
+@pytest.mark.parametrize("name", tc.case_names() + tc.long_case_names())
 def test_device_targets_equal_the_host_restatement(dev, name):
     c = tc.case(name)
     host = tc.host_targets(c)
@@ -83,7 +83,8 @@ def test_device_targets_equal_the_reference_fixture(dev, tag):
     tc.assert_item_equals_fixture(item, fx, points=False)
 
 
-@pytest.mark.parametrize("name", ["fixture_b", "fixture_c", "m3", "instance_ids_zero_only", "single_known_voxel", "negative_box"])
+@pytest.mark.parametrize("name", ["fixture_b", "fixture_c", "m3", "instance_ids_zero_only", "single_known_voxel", "negative_box",
+                                  "second_trip"])
 def test_resample_bounds_equal_pf_label_bounds(dev, name):
     """(e) The box and the union of the semantic-only and instance-only bounds of pt_resample are pf_label_bounds' words."""
     from pasco_amd.data.frame_lib import box_upper_bound, frame_lib
@@ -119,7 +120,8 @@ def _rows(g, dev, seed=0):
     return coords, 9
 
 
-@pytest.mark.parametrize("name", ["fixture_a", "fixture_c", "m3_crop", "kitti360_classes", "no_instances"])
+@pytest.mark.parametrize("name", ["fixture_a", "fixture_c", "m3_crop", "kitti360_classes", "no_instances", "second_trip",
+                                  "second_trip_crop"])
 @pytest.mark.parametrize("with_unknown", [False, True])
 def test_pack_equals_pack_targets_of_the_materialised_masks(dev, name, with_unknown):
     """(f) words, flags and oob, bit for bit; rows outside the grid included."""
@@ -157,6 +159,60 @@ def test_more_than_128_targets_masks_are_correct_and_pack_raises(dev):
     coords, _ = _rows(g, dev)
     with pytest.raises(ValueError, match="at most"):
         g["mask_label"].pack(coords, None, g["min_C"].tolist())
+
+
+def _flat_labels(seed=11):
+    """Synthetic uint8 label arrays of tc.LONG_FLAT voxels (host): classes and instance ids whose first voxel lies in every trip
+    of a capped grid, one class and one id in the last, partial wave alone."""
+    n = tc.LONG_FLAT
+    rng = np.random.default_rng(seed)
+    sem = rng.choice(np.array([0, 255, 3, 9, 14], np.uint8), n, p=[0.4, 0.1, 0.2, 0.2, 0.1])
+    ins = rng.choice(np.array([0, 1, 7], np.uint8), n, p=[0.9, 0.05, 0.05])
+    trip = tc.MAX_BLOCKS * tc.BLOCK
+    for k in range(1, -(-n // trip)):                 # a class and an id that appear first in trip k
+        at = k * trip + 100 * k + 3
+        sem[at:] = np.where(sem[at:] == (3 if k == 1 else 19 + k), 20 + k, sem[at:])
+        ins[at + 5::97] = 100 + k
+    sem[n - 2], ins[n - 1] = 77, 200                  # the last wave of the last trip: 4 voxels
+    assert n % 64 == 4 and n % 4 == 0 and tc.trips(n) == 5 and tc.trips(n // 4) == 2
+    return sem, ins
+
+
+def test_masks_on_a_second_trip_equal_numpy(dev):
+    """pt_masks strides over n / 4 words under the grid cap: its second trip needs more than 4 x 2048 x 256 voxels."""
+    from pasco_amd.data.target_lib import target_lib
+    sem, ins = _flat_labels()
+    t = 3
+    cls_slot, ins_slot = np.full(256, -1, np.int32), np.full(256, -1, np.int32)
+    cls_slot[9], cls_slot[24], ins_slot[7] = 0, 1, 2       # class 24 exists in the second trip alone, 9 and id 7 everywhere
+    got = target_lib().masks(torch.from_numpy(sem).to(dev), torch.from_numpy(ins).to(dev), torch.from_numpy(cls_slot).to(dev),
+                             torch.from_numpy(ins_slot).to(dev), t)
+    assert got.dtype == torch.bool and tuple(got.shape) == (t, tc.LONG_FLAT)
+    cs, is_ = cls_slot[sem], ins_slot[ins]
+    want = np.stack([(cs == k) | (is_ == k) for k in range(t)])
+    assert all(want[k].any() and not want[k].all() for k in range(t))
+    assert want[:, 4 * tc.MAX_BLOCKS * tc.BLOCK:].any(axis=1).all(), "every target has voxels in the second trip"
+    assert np.array_equal(got.cpu().numpy(), want), f"{int((got.cpu().numpy() != want).sum())} of {want.size} mask voxels differ"
+
+
+def test_presence_on_later_trips_equals_numpy(dev):
+    """pt_presence over five trips of its capped grid, the last of one partial wave: the class flags, the first index of every
+    instance id and the class found there."""
+    from pasco_amd.data.target_lib import TABLE, target_lib
+    sem, ins = _flat_labels()
+    table = torch.full((TABLE,), -5, dtype=torch.int32, device=dev)
+    target_lib().presence(torch.from_numpy(sem).to(dev), torch.from_numpy(ins).to(dev), table)
+    got = table.cpu().numpy()
+    flags = np.zeros(256, np.int32)
+    flags[np.unique(sem[(sem != 0) & (sem != 255)])] = 1
+    first = np.full(256, np.iinfo(np.int32).max, np.int64)
+    ids, at = np.unique(ins, return_index=True)          # the first occurrence of every value
+    first[ids], first[0] = at, np.iinfo(np.int32).max
+    cls = np.where(first == np.iinfo(np.int32).max, 0, sem[np.minimum(first, len(sem) - 1)])
+    assert flags[77] == 1 and flags[[21, 22, 23, 24]].all() and first[200] == len(sem) - 1 and (first[[101, 102, 103, 104]] < len(sem)).all()
+    assert np.array_equal(got[:256], flags), "class flags"
+    assert np.array_equal(got[256:512], first.astype(np.int32)), "first index of every instance id"
+    assert np.array_equal(got[512:], cls.astype(np.int32)), "class at the first index"
 
 
 def _criterion_inputs(g, dev, q=12, seed=3):
@@ -245,7 +301,7 @@ def test_one_training_step_from_train_batch(dev, tmp_path):
         assert p.grad is not None and bool(torch.isfinite(p.grad).all()) and bool(p.grad.any()), name
 
 
-@pytest.mark.parametrize("name", ["m3_crop", "fixture_c"])
+@pytest.mark.parametrize("name", ["m3_crop", "fixture_c", "second_trip", "second_trip_crop"])
 def test_two_runs_give_the_same_bytes(dev, name):
     """(i)"""
     c = tc.case(name)

@@ -70,6 +70,27 @@ def test_virtual_ranks(act):
     nc.check_virtual_ranks(CPU, act)
 
 
+@pytest.mark.parametrize("n,c,act", nc.LONG_CASES, ids=[f"{n}x{c}_{a}" for n, c, a in nc.LONG_CASES])
+def test_long_case_against_the_fp64_twin(n, c, act):
+    """Tile records beyond the first wave and the first pass of the combine; the vector geometry at the net's widths."""
+    nc.check_long_case(CPU, n, c, act)
+
+
+@pytest.mark.parametrize("c", nc.MERGE_C)
+@pytest.mark.parametrize("r", nc.MERGE_R)
+def test_merge_of_unequal_records_equals_the_restatement(r, c):
+    nc.check_merge_records(CPU, r, c)
+
+
+@pytest.mark.parametrize("n", nc.LONG_ROWS)
+def test_merge_of_many_tile_records_is_the_whole(n):
+    nc.check_split_merge_long(CPU, n)
+
+
+def test_virtual_ranks_at_128_channels():
+    nc.note_long(CPU, max(nc.check_virtual_ranks(CPU, "relu", c=128).values()))
+
+
 def test_default_module_forward_is_torchs_op(oracle_registered):
     """The default route is unchanged: a training-mode `MinkowskiBatchNorm` (and a `MinkowskiSyncBatchNorm` outside a process
     group) returns the bits of torch's batch_norm and moves the running statistics as it does."""

@@ -19,6 +19,11 @@ def test_sum_of_squares_and_equal_bits_on_a_repeat():
     oc.check_norm(CPU)
 
 
+@pytest.mark.parametrize("name", list(oc.LONG_CASES))
+def test_more_chunks_than_the_grid_and_more_tensors_than_a_workgroup(name):
+    oc.check_long(CPU, name)
+
+
 def test_grad_scale():
     oc.check_grad_scale(CPU)
 

@@ -117,3 +117,12 @@ def test_mask_targets_order_and_first_voxel_class():
     assert ml["labels"].tolist() == [9, 12, 9, 5]
     assert torch.equal(ml["masks"][0], sem == 9) and torch.equal(ml["masks"][2], ins == 2) and torch.equal(ml["masks"][3], ins == 7)
     assert bool((ml["masks"][0] & ml["masks"][2]).any())
+
+
+def test_the_long_cases_are_tie_free_and_reach_a_second_trip():
+    """tests/target_cases.py `long_cases`: built on the host, held to `assert_tie_free` and to the launch classes they are there
+    for (the assertions are in the builder; tests/test_hip_targets.py runs the kernels on them)."""
+    cases = tc.long_cases()
+    assert [c.name for c in cases] == tc.long_case_names()
+    assert all(c.sem.size > tc.MAX_BLOCKS * tc.BLOCK for c in cases) and tc.trips(tc.LONG_FLAT // 4) == 2
+    assert cases[1].crop_u is not None and cases[0].crop_u is None and len(cases[0].Ts) == 2
