@@ -3,7 +3,7 @@ cross-attention `ph_attn_cross_fwd`.
 
 Kept apart from `me.backend` like `grad.lib` and `grad.rowlib`: the CPU oracle binds `me.backend._SIGNATURES` and has no gradient
 kernels.  Every method takes device tensors and enqueues on the caller's current stream; nothing synchronises.  The scratch is a
-buffer of the product backend's per-stream workspace table (`CBackend._ws`), as the forward's is: it is reused from call to call
+buffer of the product backend's per-stream scratch table (`hip_backend().scratch`, "attn_bwd"), as the forward's ("attn") is: it is reused from call to call
 in stream order and dropped by `release_stream`."""
 from __future__ import annotations
 
@@ -43,13 +43,7 @@ class AttnGradLib(FamilyLib):
 
     def _workspace(self, need: int, device: torch.device) -> torch.Tensor:
         from ..me.backend import hip_backend
-        be = hip_backend()
-        key = ("attn_bwd",) + be._stream_key(device)
-        ws = be._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            be._ws[key] = ws
-        return ws
+        return hip_backend().scratch.bytes("attn_bwd", device, need)
 
     @staticmethod
     def _shape(q, k):

@@ -2,8 +2,8 @@
 the per-pair sums of the matcher and the mask losses, the gradient of the losses, and the assignment on the host.
 
 Kept apart from `me.backend` like `grad.attnlib`.  Every device method takes device tensors and enqueues on the caller's current
-stream; nothing synchronises.  The scratch of `pair_sums` is a buffer of the product backend's per-stream workspace table
-(`CBackend._ws`): reused from call to call in stream order and dropped by `release_stream`.  `assign` takes a CPU tensor: it is
+stream; nothing synchronises.  The scratch of `pair_sums` is a buffer of the product backend's per-stream scratch table
+(`hip_backend().scratch`, "pair_sums"): reused from call to call in stream order and dropped by `release_stream`.  `assign` takes a CPU tensor: it is
 the one host entry point."""
 from __future__ import annotations
 
@@ -67,13 +67,7 @@ class MatchLib(FamilyLib):
 
     def _workspace(self, need: int, device: torch.device) -> torch.Tensor:
         from ..me.backend import hip_backend
-        be = hip_backend()
-        key = ("pair_sums",) + be._stream_key(device)
-        ws = be._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(max(need, 4), dtype=torch.uint8, device=device)
-            be._ws[key] = ws
-        return ws
+        return hip_backend().scratch.bytes("pair_sums", device, need, floor=4)
 
     def target_pack(self, masks, unknown, coords, origin=(0, 0, 0)):
         """masks uint8 [T,X,Y,Z], unknown uint8 [X,Y,Z] | None, coords int32 [N,4] -> (tbits int32 [N,4], flags uint8 [N],

@@ -4,7 +4,7 @@ sorted order, and the gradient of both losses in one pass.
 
 Kept apart from `me.backend` like `grad.matchlib`.  Every method takes device tensors and enqueues on the caller's current
 stream; nothing synchronises.  The scratch of a forward (keys, order and the three stages' partials: `geometry(n, c)`) is ONE
-buffer of the product backend's per-stream workspace table (`CBackend._ws`): reused from call to call in stream order and
+buffer of the product backend's per-stream scratch table (`hip_backend().scratch`, "semloss"): reused from call to call in stream order and
 dropped by `release_stream`."""
 from __future__ import annotations
 
@@ -91,15 +91,7 @@ class SemLib(FamilyLib):
 
     def _workspace(self, need: int, device: torch.device) -> torch.Tensor:
         from ..me.backend import hip_backend
-        be = hip_backend()
-        key = ("semloss",) + be._stream_key(device)
-        ws = be._ws.get(key)
-        if ws is None or ws.numel() < need:
-            be._ws.pop(key, None)       # drop the smaller buffer before the larger one is allocated
-            ws = None
-            ws = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
-            be._ws[key] = ws
-        return ws
+        return hip_backend().scratch.bytes("semloss", device, need, floor=256)
 
     @staticmethod
     def parts(ws: torch.Tensor, n: int, c: int, g: dict):

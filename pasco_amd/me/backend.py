@@ -12,11 +12,11 @@ import contextlib
 import ctypes as C
 import os
 import threading
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
-from .._clib import _raw_stream, bind
+from .._clib import StreamScratch, _raw_stream, bind
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(os.path.dirname(_HERE), "csrc", "libpascohip.so")
@@ -172,29 +172,23 @@ class CBackend:
             raise RuntimeError(f"{path}: sizeof(ph_conv_desc) = {None if dsz is None else int(dsz())}, the binding's mirror has "
                                f"{C.sizeof(ConvDesc)} bytes - rebuild the library against include/pasco_hip.h")
         self.fn = bind(self.lib, prefix, _SIGNATURES, _RESTYPES)
-        self._ws: Dict[torch.device, torch.Tensor] = {}
-        self._status_ptrs: Dict[tuple, int] = {}         # (device type, index, stream handle) -> address of the status pair
+        self.scratch = StreamScratch()       # workspaces, split-K scratch, attention partials, the status pair: per (device, stream)
         self._tls = threading.local()
         # tests may let a CPU checker library take the split-operand (mode 2) descriptors as well, so that the
         # host-side plumbing of that path (operand emission, split-only tensors) is exercised without a GPU
         self.checker_split = False
 
     # -- helpers -----------------------------------------------------------------------------------
+    @contextlib.contextmanager
     def routing(self, bits: int):
         """Context manager for parity tests: every `conv_fwd` of THIS thread inside it carries `ph_conv_desc.route = bits`
         (ROUTE_* below = PH_ROUTE_* of include/pasco_hip.h: pin the window / gather, wide / not, row-stream / not kernel of a shape
         that several kernels can serve).  Per call, no process-global state; the product path never sets it."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def cm():
-            old = getattr(self._tls, "route", 0)
-            self._tls.route = int(bits)
-            try:
-                yield self
-            finally:
-                self._tls.route = old
-        return cm()
+        old = self.set_route(bits)
+        try:
+            yield self
+        finally:
+            self._tls.route = old
 
     def set_route(self, bits: int) -> int:
         """`ph_conv_desc.route` of this thread's following `conv_fwd` calls (see `routing`); returns the previous value."""
@@ -220,40 +214,15 @@ class CBackend:
             return _raw_stream(idx)
         return None
 
-    def _stream_key(self, device: torch.device):
-        """Scratch buffers are reused from launch to launch, which is only safe in stream order: one set per
-        (device, stream)."""
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        return (device, self.stream(device) or 0)
-
     def release_stream(self, stream) -> int:
         """Drop every per-stream buffer (workspaces, split-K scratch, attention partials, the status pair) this backend keeps
         for `stream` (a torch.cuda.Stream or a raw handle): call it when a serving loop retires a stream - the buffers are
         keyed by the raw handle, so they would otherwise outlive it, and a later stream that is handed the same handle would
         inherit them together with any status bit nobody read.  Returns the number of buffers dropped."""
-        handle = int(getattr(stream, "cuda_stream", stream) or 0)
-        dev = getattr(stream, "device", None)
-        if dev is None and torch.cuda.is_available():      # a raw handle: the streams of the current device
-            dev = torch.device("cuda", torch.cuda.current_device())
-        # per-stream entries are exactly the (name, device, handle) keys `_stream_key` makes: nothing else is touched
-        drop = [k for k in self._ws
-                if isinstance(k, tuple) and len(k) == 3 and isinstance(k[0], str) and isinstance(k[1], torch.device)
-                and k[2] == handle and (dev is None or k[1] == dev)]
-        for k in drop:
-            del self._ws[k]
-        for k in [k for k in self._status_ptrs if k[2] == handle and (dev is None or k[1] == dev.index)]:
-            del self._status_ptrs[k]
-        return len(drop)
+        return self.scratch.release(stream)
 
     def workspace(self, n: int, device: torch.device) -> torch.Tensor:
-        need = int(self.fn["workspace_bytes"](int(n)))
-        key = ("ws",) + self._stream_key(device)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=device)
-            self._ws[key] = ws
-        return ws
+        return self.scratch.bytes("ws", device, int(self.fn["workspace_bytes"](int(n))), floor=1 << 20)
 
     def _chk(self, t: torch.Tensor, dtype, name: str):
         # ~900 calls per step: the passing case is three attribute tests, no torch.device object
@@ -265,6 +234,15 @@ class CBackend:
             raise ValueError(f"{name}: tensor must be contiguous")
         if t.device.type != self.device_type:
             raise ValueError(f"{name}: tensor on {t.device}, backend serves {self.device_type}")
+
+    def _chk_vec(self, t: Optional[torch.Tensor], n: int, name: str, who: str):
+        """An optional per-channel fp32 vector of `n` entries (`who` = "conv" / "split_rows" opens the message).  Several per
+        convolution launch: the passing case is `_chk`'s three tests and the count, in this frame."""
+        if t is None or (t.dtype is torch.float32 and t.is_cuda == self._serves_cuda and t.is_contiguous() and t.numel() == n):
+            return
+        self._chk(t, torch.float32, name)
+        if t.numel() != n:
+            raise ValueError(f"{who}: {name} has {t.numel()} entries, expected {n}")
 
     # -- coordinate maps ---------------------------------------------------------------------------
     @staticmethod
@@ -438,6 +416,40 @@ class CBackend:
         `status` (int32 [1] device word): the launch reports its flags there instead of into the stream's status pair;
         `exact_if` (exact fp32 launches only): the launch does its work only when bit 0 of that word is set - the guarded
         form of the split path (include/pasco_hip.h ph_conv_desc.exact_if; `pasco_amd.me.modules`)."""
+        x, dev, kvol, cin, cout = self._conv_operands(x, weight, nbr, n_out, xshape, wshape, split, in_split, pro_scale, pro_shift,
+                                                      pro_act)
+        mode2 = split is not None and len(split) == 2
+        emit = emit_split is not None and mode2 and cout % 32 == 0
+        if emit_split is not None and not emit:
+            raise ValueError("conv: emit_split needs a mode-2 split and cout % 32 == 0")
+        if out is None and (want_out or not emit):
+            out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
+        if emit and out_split is not None:       # caller-owned operand rows (a row slice of a larger operand tensor)
+            if out_split.dtype != torch.float16 or not out_split.is_contiguous() or out_split.numel() != n_out * 2 * cout:
+                raise ValueError("conv: out_split must be contiguous f16 [n_out, cout / 32, 2, 32]")
+        else:
+            out_split = torch.empty((n_out, cout // 32, 2, 32), dtype=torch.float16, device=dev) if emit else None
+        if n_out == 0:
+            return (out, out_split) if emit else out
+        d = ConvDesc()
+        d.route = getattr(self._tls, "route", 0)
+        d.in_, d.weight, d.nbr, d.out = (None if x.is_meta else _ptr(x)), _ptr(weight), _ptr(nbr), _ptr(out)
+        d.n_in, d.n_out, d.cin, d.cout, d.kvol = x.shape[0], n_out, cin, cout, kvol
+        d.pro_act, d.epi_act, d.res_act, d.epi_slope = pro_act, epi_act, res_act, float(slope)
+        self._desc_affine(d, n_out, cin, cout, pro_scale, pro_shift, bias, epi_scale, epi_shift, epi2_scale, epi2_shift, residual,
+                          axis, mode2, emit_split if emit else None, out_split)
+        if split is not None:      # opt-in f16x3 products (an operand made there is kept here: it has to live until the launch)
+            in_split = self._desc_split(d, x, nbr, dev, n_out, kvol, cin, cout, split, in_split, in_split_has_prologue, pro_scale,
+                                        pro_shift, pro_act, slope, grid, rowlist, win, status)
+        if exact_if is not None:
+            if split is not None:
+                raise ValueError("conv: exact_if guards an exact fp32 launch (no split)")
+            d.exact_if = exact_if.data_ptr()
+        self._check(self.fn["conv_fwd"](C.byref(d), self.stream(dev)), "conv_fwd")
+        return (out, out_split) if emit else out
+
+    def _conv_operands(self, x, weight, nbr, n_out, xshape, wshape, split, in_split, pro_scale, pro_shift, pro_act):
+        """The rows, the kernel and the map of one `conv_fwd`, checked -> (x or a meta tensor of its shape, device, kvol, cin, cout)."""
         if x is None:          # rows that exist only as a pre-split operand (mode 2): `xshape` = (n_in, cin)
             if xshape is None or in_split is None or split is None or len(split) != 2 or not self.split_capable():
                 raise ValueError("conv: x=None needs xshape, in_split and a mode-2 split on the device backend")
@@ -454,122 +466,95 @@ class CBackend:
             kvol, cin, cout = wshape
         else:
             self._chk(weight, torch.float32, "weight")
-            if weight.dim() == 2:
-                kvol, (cin, cout) = 1, weight.shape
-            else:
-                kvol, cin, cout = weight.shape
+            kvol, cin, cout = weight.shape if weight.dim() == 3 else (1,) + tuple(weight.shape)
         if x.shape[1] != cin:
             raise ValueError(f"conv: input has {x.shape[1]} channels, kernel expects {cin}")
         if nbr is not None:
             self._chk(nbr, torch.int32, "nbr")
             if tuple(nbr.shape) != (kvol, n_out):
                 raise ValueError(f"conv: nbr shape {tuple(nbr.shape)} != {(kvol, n_out)}")
-        emit = emit_split is not None and split is not None and len(split) == 2 and cout % 32 == 0
-        if emit_split is not None and not emit:
-            raise ValueError("conv: emit_split needs a mode-2 split and cout % 32 == 0")
-        if out is None and (want_out or not emit):
-            out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
-        if emit and out_split is not None:       # caller-owned operand rows (a row slice of a larger operand tensor)
-            if out_split.dtype != torch.float16 or not out_split.is_contiguous() or out_split.numel() != n_out * 2 * cout:
-                raise ValueError("conv: out_split must be contiguous f16 [n_out, cout / 32, 2, 32]")
-        else:
-            out_split = torch.empty((n_out, cout // 32, 2, 32), dtype=torch.float16, device=dev) if emit else None
-        if n_out == 0:
-            return (out, out_split) if emit else out
-        d = ConvDesc()
-        d.route = getattr(self._tls, "route", 0)
-        if emit:
+        return x, dev, kvol, cin, cout
+
+    def _desc_affine(self, d, n_out, cin, cout, pro_scale, pro_shift, bias, epi_scale, epi_shift, epi2_scale, epi2_shift, residual,
+                     axis, mode2, emit_split, out_split):
+        """Around the products: the emitted operand's scale and shift, the seven per-channel vectors, the residual, the per-axis table."""
+        if emit_split is not None:
             osc, osh, oact = emit_split
-            for name, t in (("osp_scale", osc), ("osp_shift", osh)):
-                if t is not None:
-                    self._chk(t, torch.float32, name)
-                    if t.numel() != cout:
-                        raise ValueError(f"conv: {name} has {t.numel()} entries, expected {cout}")
+            self._chk_vec(osc, cout, "osp_scale", "conv")
+            self._chk_vec(osh, cout, "osp_shift", "conv")
             d.out_split, d.osp_scale, d.osp_shift, d.osp_act = _ptr(out_split), _ptr(osc), _ptr(osh), int(oact)
-        d.in_, d.weight, d.nbr, d.out = (None if x.is_meta else _ptr(x)), _ptr(weight), _ptr(nbr), _ptr(out)
-        d.n_in, d.n_out, d.cin, d.cout, d.kvol = x.shape[0], n_out, cin, cout, kvol
-        d.pro_act, d.epi_act, d.res_act, d.epi_slope = pro_act, epi_act, res_act, float(slope)
-        for name, t, c in (("pro_scale", pro_scale, cin), ("pro_shift", pro_shift, cin),
-                           ("bias", bias, cout), ("epi_scale", epi_scale, cout),
-                           ("epi_shift", epi_shift, cout), ("epi2_scale", epi2_scale, cout),
+        for name, t, c in (("pro_scale", pro_scale, cin), ("pro_shift", pro_shift, cin), ("bias", bias, cout),
+                           ("epi_scale", epi_scale, cout), ("epi_shift", epi_shift, cout), ("epi2_scale", epi2_scale, cout),
                            ("epi2_shift", epi2_shift, cout)):
             if t is not None:
-                self._chk(t, torch.float32, name)
-                if t.numel() != c:
-                    raise ValueError(f"conv: {name} has {t.numel()} entries, expected {c}")
-            setattr(d, name, _ptr(t))
+                self._chk_vec(t, c, name, "conv")
+                setattr(d, name, t.data_ptr())
         if residual is not None:
             self._chk(residual, torch.float32, "residual")
             if tuple(residual.shape) != (n_out, cout):
                 raise ValueError("conv: residual shape mismatch")
-        d.residual = _ptr(residual)
+            d.residual = residual.data_ptr()
         if axis is not None:
             tab, acoords, lo = axis
             self._chk(tab, torch.float32, "axis table")
             self._chk(acoords, torch.int32, "axis coords")
             if tab.dim() != 3 or tab.shape[0] != 3 or tab.shape[2] != cout or tuple(acoords.shape) != (n_out, 4):
                 raise ValueError("conv: axis = (table [3, T, cout], coords [n_out, 4], lo)")
-            if self.device_type == "cuda" and (split is None or len(split) != 2):
+            if self.device_type == "cuda" and not mode2:
                 raise ValueError("conv: the axis-table residual is served by the pre-split (mode 2) path")
             d.axis_table, d.axis_coords, d.axis_lo, d.axis_rows = _ptr(tab), _ptr(acoords), int(lo), int(tab.shape[1])
-        if split is not None:      # opt-in f16x3 products
-            if len(split) == 2:    # (w_split, unscale) from split_weight_rows + in_split from split_rows: mode 2
-                w_split, unscale = split
-                if in_split is None:
-                    in_split = self.split_rows(x, pro_scale=pro_scale, pro_shift=pro_shift, pro_act=pro_act, slope=slope)
-                elif not x.is_meta and (pro_scale is not None or pro_shift is not None or pro_act != ACT_NONE) and \
-                        not in_split_has_prologue:
-                    # the device library never applies a prologue in mode 2: a caller-made operand must already carry it
-                    raise ValueError("conv: in_split given together with a prologue - pass in_split_has_prologue=True if "
-                                     "the operand was built with split_rows(x, pro_scale=..., pro_shift=..., pro_act=...), "
-                                     "else drop in_split")
-                cpad = (cin + 31) // 32 * 32
-                if in_split.dtype != torch.float16 or in_split.numel() != x.shape[0] * 2 * cpad:
-                    raise ValueError("conv: in_split does not match the input rows")
-                if w_split.numel() != kvol * cout * 2 * cpad:
-                    raise ValueError("conv: w_split does not match the kernel")
-                d.mma_mode, d.in_split, d.w_split = 2, _ptr(in_split), _ptr(w_split)
-                if grid is not None and nbr is not None:
-                    gd, gk = grid
-                    if len(gd) != 4 or len(gk) != 3 or gd[0] * gd[1] * gd[2] * gd[3] != n_out or x.shape[0] != n_out or \
-                            gk[0] * gk[1] * gk[2] != kvol or any(k % 2 == 0 for k in gk):
-                        raise ValueError("conv: grid = ((B, X, Y, Z), (kx, ky, kz)) must describe the whole map (odd kernel sizes)")
-                    for q in range(4):
-                        d.grid_dims[q] = int(gd[q])
-                    for q in range(3):
-                        d.grid_kernel[q] = int(gk[q])
-                if rowlist is not None and nbr is not None:     # one-pair-per-row map: k = 1 products per list tile
-                    d.rl_in, d.rl_out, d.rl_tile_k = _ptr(rowlist["in"]), _ptr(rowlist["out"]), _ptr(rowlist["tile_k"])
-                    d.rl_rows, d.rl_tiles = int(rowlist["in"].numel()), int(rowlist["tile_k"].numel())
-                if win is not None and kvol == 27 and nbr is not None:
-                    d.win_rows, d.win_cnt, d.win_slots, d.win_stats = (_ptr(win["rows"]), _ptr(win["cnt"]),
-                                                                       _ptr(win["slots"]), _ptr(win["stats"]))
-                    if 32 < cout <= 64 and self._serves_cuda:       # the window kernel of the 64-wide outputs reads its weights in
-                        d.w_frag = _ptr(self.weight_fragments(w_split, kvol, cout, cpad))     # fragment order (cached on w_split)
-            else:                  # (w_hi, w_lo, unscale) from split_weight_f16: mode 1, activations split in-kernel
-                w_hi, w_lo, unscale = split
-                d.mma_mode, d.w_f16_hi, d.w_f16_lo = 1, _ptr(w_hi), _ptr(w_lo)
-            d.split_exp2 = SPLIT_ACT_EXP2
-            d.w_unscale = float(unscale) * 2.0 ** (-SPLIT_ACT_EXP2)
-            d.status = self.status_ptr(dev) if status is None else status.data_ptr()
-            if kvol > 1 or n_out * cout <= (1 << 23):
-                # scratch for a split over the kernel offsets: few-row layers split whole (up to 12 partial copies), big maps only
-                # their last partial round of row tiles (ph_conv_dma_try's tail split: slices x tail tiles <= the 512 resident
-                # 128 x 128 tiles of one round = 32 MiB of fp32 partial sums whatever the width)
-                need = 12 * n_out * cout * 4 if n_out * cout <= (1 << 23) else 512 * 128 * 128 * 4
-                key = ("splitk",) + self._stream_key(dev)
-                sk = self._ws.get(key)
-                if sk is None or sk.numel() < need:
-                    sk = torch.empty(need, dtype=torch.uint8, device=dev)
-                    self._ws[key] = sk
-                d.splitk_ws, d.splitk_ws_bytes = _ptr(sk), sk.numel()
-        if exact_if is not None:
-            if split is not None:
-                raise ValueError("conv: exact_if guards an exact fp32 launch (no split)")
-            d.exact_if = exact_if.data_ptr()
-        rc = self.fn["conv_fwd"](C.byref(d), self.stream(dev))
-        self._check(rc, "conv_fwd")
-        return (out, out_split) if emit else out
+
+    def _desc_split(self, d, x, nbr, dev, n_out, kvol, cin, cout, split, in_split, in_split_has_prologue, pro_scale, pro_shift,
+                    pro_act, slope, grid, rowlist, win, status):
+        """The f16x3 products: the operands of mode 1 or mode 2 (and mode 2's routes), their scale, the status word, split-K scratch.
+        -> the input operand of mode 2, which may have been made here."""
+        if len(split) == 2:    # (w_split, unscale) from split_weight_rows + in_split from split_rows: mode 2
+            w_split, unscale = split
+            if in_split is None:
+                in_split = self.split_rows(x, pro_scale=pro_scale, pro_shift=pro_shift, pro_act=pro_act, slope=slope)
+            elif not x.is_meta and (pro_scale is not None or pro_shift is not None or pro_act != ACT_NONE) and \
+                    not in_split_has_prologue:
+                # the device library never applies a prologue in mode 2: a caller-made operand must already carry it
+                raise ValueError("conv: in_split given together with a prologue - pass in_split_has_prologue=True if "
+                                 "the operand was built with split_rows(x, pro_scale=..., pro_shift=..., pro_act=...), "
+                                 "else drop in_split")
+            cpad = (cin + 31) // 32 * 32
+            if in_split.dtype != torch.float16 or in_split.numel() != x.shape[0] * 2 * cpad:
+                raise ValueError("conv: in_split does not match the input rows")
+            if w_split.numel() != kvol * cout * 2 * cpad:
+                raise ValueError("conv: w_split does not match the kernel")
+            d.mma_mode, d.in_split, d.w_split = 2, in_split.data_ptr(), w_split.data_ptr()
+            if nbr is not None:
+                self._desc_routes(d, x.shape[0], n_out, kvol, cout, cpad, w_split, grid, rowlist, win)
+        else:                  # (w_hi, w_lo, unscale) from split_weight_f16: mode 1, activations split in-kernel
+            w_hi, w_lo, unscale = split
+            d.mma_mode, d.w_f16_hi, d.w_f16_lo = 1, _ptr(w_hi), _ptr(w_lo)
+        d.split_exp2, d.w_unscale = SPLIT_ACT_EXP2, float(unscale) * 2.0 ** (-SPLIT_ACT_EXP2)
+        d.status = self.status_ptr(dev) if status is None else status.data_ptr()
+        if kvol > 1 or n_out * cout <= (1 << 23):
+            # scratch for a split over the kernel offsets: few-row layers split whole (up to 12 partial copies), big maps only
+            # their last partial round of row tiles (ph_conv_dma_try's tail split: slices x tail tiles <= the 512 resident
+            # 128 x 128 tiles of one round = 32 MiB of fp32 partial sums whatever the width)
+            need = 12 * n_out * cout * 4 if n_out * cout <= (1 << 23) else 512 * 128 * 128 * 4
+            sk = self.scratch.bytes("splitk", dev, need)
+            d.splitk_ws, d.splitk_ws_bytes = sk.data_ptr(), sk.numel()
+        return in_split
+
+    def _desc_routes(self, d, n_in, n_out, kvol, cout, cpad, w_split, grid, rowlist, win):
+        """What lets another kernel serve a mode-2 launch that has a kernel map: the dense-grid promise, row lists, input windows."""
+        if grid is not None:
+            gd, gk = grid
+            if len(gd) != 4 or len(gk) != 3 or gd[0] * gd[1] * gd[2] * gd[3] != n_out or n_in != n_out or \
+                    gk[0] * gk[1] * gk[2] != kvol or any(k % 2 == 0 for k in gk):
+                raise ValueError("conv: grid = ((B, X, Y, Z), (kx, ky, kz)) must describe the whole map (odd kernel sizes)")
+            d.grid_dims[:], d.grid_kernel[:] = [int(v) for v in gd], [int(v) for v in gk]
+        if rowlist is not None:     # one-pair-per-row map: k = 1 products per list tile
+            d.rl_in, d.rl_out, d.rl_tile_k = _ptr(rowlist["in"]), _ptr(rowlist["out"]), _ptr(rowlist["tile_k"])
+            d.rl_rows, d.rl_tiles = int(rowlist["in"].numel()), int(rowlist["tile_k"].numel())
+        if win is not None and kvol == 27:
+            d.win_rows, d.win_cnt, d.win_slots, d.win_stats = _ptr(win["rows"]), _ptr(win["cnt"]), _ptr(win["slots"]), _ptr(win["stats"])
+            if 32 < cout <= 64 and self._serves_cuda:       # the window kernel of the 64-wide outputs reads its weights in
+                d.w_frag = _ptr(self.weight_fragments(w_split, kvol, cout, cpad))     # fragment order (cached on w_split)
 
     @staticmethod
     def grid_offsets(kernel_size) -> list:
@@ -595,20 +580,9 @@ class CBackend:
         return self._status_pair(device)[0:1]
 
     def status_ptr(self, device) -> int:
-        """Address of `status_word(device)` - what the launches take.  ~260 calls per step: the address of a stream's pair is
-        looked up by (device index, raw stream handle) without building a torch.device, a key tuple or a one-element view."""
+        """Address of `status_word(device)` - what the launches take (~260 calls per step: `StreamScratch.status_ptr`)."""
         pinned = getattr(self._tls, "status_pin", None)
-        if pinned is not None:
-            return pinned.data_ptr()
-        idx = device.index
-        if idx is None and device.type == "cuda":
-            idx = torch.cuda.current_device()
-        k = (device.type, idx, _raw_stream(idx) if device.type == "cuda" else 0)
-        hit = self._status_ptrs.get(k)
-        if hit is None:
-            hit = self._status_pair(device).data_ptr()
-            self._status_ptrs[k] = hit
-        return hit
+        return self.scratch.status_ptr(device) if pinned is None else pinned.data_ptr()
 
     def optimistic_word(self, device) -> torch.Tensor:
         """Second word of the stream's status pair: kernels and torch ops OR a non-zero value into it when an OPTIMISTIC
@@ -619,17 +593,7 @@ class CBackend:
 
     def _status_pair(self, device) -> torch.Tensor:
         pinned = getattr(self._tls, "status_pin", None)
-        if pinned is not None:
-            return pinned
-        key = ("status",) + self._stream_key(torch.device(device))
-        t = self._ws.get(key)
-        if t is None:
-            # cleared in place by every later `check_status`: a pair first made under torch.inference_mode() would be an
-            # inference tensor, which no call outside that mode may write to
-            with torch.inference_mode(False):
-                t = torch.zeros(2, dtype=torch.int32, device=device)
-            self._ws[key] = t
-        return t
+        return self.scratch.words("status", device, 2) if pinned is None else pinned
 
     @contextlib.contextmanager
     def pin_status(self, device):
@@ -637,8 +601,7 @@ class CBackend:
         for work that is recorded on another stream but belongs to this one (hipGraph capture runs on a capture stream;
         the replay is launched on, and checked from, the caller's stream)."""
         prev = getattr(self._tls, "status_pin", None)
-        self._tls.status_pin = None
-        self._tls.status_pin = self._status_pair(device)
+        self._tls.status_pin = self.scratch.words("status", device, 2)       # the stream's own pair, whatever is pinned now
         try:
             yield
         finally:
@@ -666,7 +629,7 @@ class CBackend:
         per-axis table clamped a coordinate.  One device->host read (call where the host synchronises anyway); read and
         clear are two stream-ordered operations on the stream's own word.  Every raised bit is reported; the exception is
         an `F16RangeError` when bit 0 is the only one (the caller may redo the step on the exact path)."""
-        t = self._ws.get(("status",) + self._stream_key(torch.device(device)))
+        t = self.scratch.get("status", device)
         if t is None:
             return
         snap = t.clone()          # stream-ordered: after every kernel of this stream that could raise a flag ...
@@ -684,20 +647,24 @@ class CBackend:
         raise (F16RangeError if v == 1 else StatusError)(v, text)
 
     @staticmethod
+    def _weight_exponent(weight: torch.Tensor, exponent=None):
+        """-> (weight * 2^e as fp32 [K, cout, cin], e): the largest magnitude just below 2^14 (a host read unless `exponent` is given)."""
+        w = weight.detach().float()
+        if w.dim() == 2:
+            w = w[None]
+        if exponent is None:
+            wmax = float(w.abs().max())
+            exponent = 0 if wmax == 0.0 else 13 - int(torch.frexp(torch.tensor(wmax))[1])
+        e = int(exponent)
+        return (w * float(2.0 ** e)).transpose(1, 2).contiguous(), e     # exact power of two (torch.ldexp goes through pow on the GPU: inexact)
+
+    @staticmethod
     def split_weight_f16(weight: torch.Tensor, exponent=None):
         """fp32 kernel [K, cin, cout] (or [cin, cout]) -> (hi, lo) f16 [K, cout, cin] of weight * 2^e and the
         factor 2^-e.  e puts the largest magnitude just below 2^14 so that every lo part is a normal f16
         (one device->host read; static weights are split once and cached).  Pass `exponent` to skip the
         read for per-call operands of known magnitude."""
-        w = weight.detach().float()
-        if w.dim() == 2:
-            w = w[None]
-        if exponent is not None:
-            e = int(exponent)
-        else:
-            wmax = float(w.abs().max())
-            e = 0 if wmax == 0.0 else 13 - int(torch.frexp(torch.tensor(wmax))[1])
-        scaled = (w * float(2.0 ** e)).transpose(1, 2).contiguous()   # exact power of two (torch.ldexp goes through pow on the GPU: inexact)
+        scaled, e = CBackend._weight_exponent(weight, exponent)
         hi = scaled.to(torch.float16)
         lo = (scaled - hi.float()).to(torch.float16)
         return hi.contiguous(), lo.contiguous(), float(2.0 ** (-e))
@@ -716,11 +683,8 @@ class CBackend:
         cpad = (c + 31) // 32 * 32
         if out is None:
             out = torch.empty((n, cpad // 32, 2, 32), dtype=torch.float16, device=x.device)
-        for name, t in (("pro_scale", pro_scale), ("pro_shift", pro_shift)):
-            if t is not None:
-                self._chk(t, torch.float32, name)
-                if t.numel() != c:
-                    raise ValueError(f"split_rows: {name} has {t.numel()} entries, expected {c}")
+        self._chk_vec(pro_scale, c, "pro_scale", "split_rows")
+        self._chk_vec(pro_shift, c, "pro_shift", "split_rows")
         rc = self.fn["split_rows"](_ptr(x), n, c, _ptr(pro_scale), _ptr(pro_shift), pro_act, float(slope), exp2, _ptr(out),
                                    self.status_ptr(x.device) if status is None else status.data_ptr(), self.stream(x.device))
         self._check(rc, "split_rows")
@@ -729,17 +693,8 @@ class CBackend:
     def split_weight_rows(self, weight: torch.Tensor, exponent=None):
         """fp32 kernel [K, cin, cout] (or [cin, cout]) -> (w_split, 2^-e): the mode-2 operand of weight * 2^e,
         transposed to [K, cout, cin] rows and split by `split_rows` (static weights: once, cached by callers)."""
-        w = weight.detach().float()
-        if w.dim() == 2:
-            w = w[None]
-        if exponent is not None:
-            e = int(exponent)
-        else:
-            wmax = float(w.abs().max())
-            e = 0 if wmax == 0.0 else 13 - int(torch.frexp(torch.tensor(wmax))[1])
-        k, cin, cout = w.shape
-        rows = (w * float(2.0 ** e)).transpose(1, 2).contiguous().view(k * cout, cin)   # exact power of two
-        return self.split_rows(rows, exp2=0), float(2.0 ** (-e))
+        scaled, e = CBackend._weight_exponent(weight, exponent)
+        return self.split_rows(scaled.view(-1, scaled.shape[2]), exp2=0), float(2.0 ** (-e))
 
     @staticmethod
     def weight_fragments(w_split: torch.Tensor, kvol: int, cout: int, cpad: int) -> torch.Tensor:
@@ -994,13 +949,7 @@ class CBackend:
                 raise ValueError("keep_mask: coords [n, 4], corners [3]")
         out = torch.empty((n,), dtype=torch.bool, device=dev)
         ptrs = (_vp * len(srcs))(*[_ptr(t) for t in srcs])
-        word = None
-        if fallback_rows > 0:
-            key = ("keep_any",) + self._stream_key(dev)
-            word = self._ws.get(key)
-            if word is None:
-                word = torch.zeros(1, dtype=torch.int32, device=dev)
-                self._ws[key] = word
+        word = self.scratch.words("keep_any", dev, 1) if fallback_rows > 0 else None
         rc = self.fn["keep_mask"](C.cast(ptrs, _vp), len(srcs), kind, _ptr(coords) if lo is not None else None, n, _ptr(lo),
                                   _ptr(hi), int(fallback_rows), _ptr(out), _ptr(word), self.stream(dev))
         self._check(rc, "keep_mask")
@@ -1086,6 +1035,9 @@ class CBackend:
     def attn_supported(self, qn: int, dh: int) -> bool:
         return qn <= 128 and (dh == 48 or self.device_type == "cpu")
 
+    def _attn_workspace(self, n, b, h, qn, d, device) -> torch.Tensor:
+        return self.scratch.bytes("attn", device, int(self.fn["attn_workspace_bytes"](n, b, h, qn, d)))
+
     def attn_cross_fwd(self, q, k, v, bits=None, any_=None) -> torch.Tensor:
         """q [B,H,Qn,Dh] (pre-scaled), k/v [B,N,H*Dh] -> out [B,Qn,H*Dh]."""
         for t, nm in ((q, "q"), (k, "k"), (v, "v")):
@@ -1094,17 +1046,11 @@ class CBackend:
         n = k.shape[1]
         assert k.shape == (b, n, h * dh) and v.shape == k.shape
         out = torch.empty((b, qn, h * dh), dtype=torch.float32, device=q.device)
-        need = int(self.fn["attn_workspace_bytes"](n, b, h, qn, dh))
-        key = ("attn",) + self._stream_key(q.device)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-            self._ws[key] = ws
+        ws = self._attn_workspace(n, b, h, qn, dh, q.device)
         rc = self.fn["attn_cross_fwd"](_ptr(q), _ptr(k), _ptr(v), _ptr(bits), _ptr(any_), _ptr(out), n, b, h, qn, dh,
                                        _ptr(ws), ws.numel(), self.stream(q.device))
         self._check(rc, "attn_cross_fwd")
         return out
-
 
     def attn_cross_split(self, q, k_split, v_split, n: int, bits=None, any_=None, exp2=None) -> torch.Tensor:
         """attn_cross_fwd on split f16 K / V operands ([B*N, H*Dh/32, 2, 32] f16 each, value * 2^exp2; what
@@ -1116,18 +1062,12 @@ class CBackend:
             assert t.dtype == torch.float16 and t.is_contiguous() and t.numel() == b * n * d * 2, nm
         exp2 = SPLIT_ACT_EXP2 if exp2 is None else int(exp2)
         out = torch.empty((b, qn, d), dtype=torch.float32, device=q.device)
-        need = int(self.fn["attn_workspace_bytes"](n, b, h, qn, dh))
-        key = ("attn",) + self._stream_key(q.device)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-            self._ws[key] = ws
+        ws = self._attn_workspace(n, b, h, qn, dh, q.device)
         rc = self.fn["attn_cross_split"](_ptr(q), _ptr(k_split), _ptr(v_split), exp2, _ptr(bits), _ptr(any_), _ptr(out),
                                          n, b, h, qn, dh, _ptr(ws), ws.numel(), self.status_ptr(q.device),
                                          self.stream(q.device))
         self._check(rc, "attn_cross_split")
         return out
-
 
     POS_AUG_COLS = 16
 
@@ -1158,12 +1098,7 @@ class CBackend:
         assert aug.dtype == torch.float16 and aug.is_contiguous() and aug.numel() == b * n * self.POS_AUG_COLS, "aug"
         exp2 = SPLIT_ACT_EXP2 if exp2 is None else int(exp2)
         out = torch.empty((b, qn, h * d), dtype=torch.float32, device=q2.device)
-        need = int(self.fn["attn_workspace_bytes"](n, b, h, qn, d))
-        key = ("attn",) + self._stream_key(q2.device)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=q2.device)
-            self._ws[key] = ws
+        ws = self._attn_workspace(n, b, h, qn, d, q2.device)
         rc = self.fn["attn_cross_feat"](_ptr(q2), _ptr(x_split), _ptr(aug), c, exp2, _ptr(bits), _ptr(any_), _ptr(out), n, b, h,
                                         qn, _ptr(ws), ws.numel(), self.status_ptr(q2.device), self.stream(q2.device))
         self._check(rc, "attn_cross_feat")

@@ -109,7 +109,7 @@ def test_release_stream_drops_the_per_stream_buffers(oracle):
     dev = torch.device("cpu")
     oracle.workspace(1000, dev)
     oracle.status_word(dev).fill_(1)
-    assert any(k[0] == "status" for k in oracle._ws)
+    assert {"status", "ws"} <= oracle.scratch.held()
     assert oracle.release_stream(0) >= 2
-    assert not any(isinstance(k, tuple) and k[0] in ("status", "ws") for k in oracle._ws)
+    assert not {"status", "ws"} & oracle.scratch.held()
     assert int(oracle.status_word(dev)) == 0          # a fresh pair

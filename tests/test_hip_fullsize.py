@@ -267,9 +267,24 @@ def test_scene_server_close_restores_what_it_changed(hip):
     handles = {int(s.cuda_stream) for s in server.streams}
     graphs = net.transformer_predictor.__dict__.get("_qgraphs", {})
     assert any(k[-1] in handles for k in graphs) or net.transformer_predictor.query_graph_state() != "graph"
-    assert any(k[2] in handles for k in hip._status_ptrs), "the workers' status pairs are cached by stream handle"
+    streams = list(server.streams)
+    assert all("status" in hip.scratch.held(s) for s in streams), "every worker stream holds its status pair"
+    for s in streams:
+        with torch.cuda.stream(s):
+            hip.status_ptr(dev)                           # the address is cached by stream handle
+            hip.status_word(dev).fill_(1)                 # a flag nobody read
+    torch.cuda.synchronize()
     server.close()
     assert sys.getswitchinterval() == before
     assert not any(k[-1] in handles for k in net.transformer_predictor.__dict__.get("_qgraphs", {}))
-    assert not any(k[2] in handles for k in hip._status_ptrs)
-    assert not any(isinstance(k, tuple) and len(k) == 3 and k[2] in handles for k in hip._ws)
+    assert all(hip.scratch.held(s) == set() for s in streams)
+    keep = []                                             # held until the end, so that no new pair can land on a freed one's block
+    for s in streams:
+        with torch.cuda.stream(s):
+            ptr = hip.status_ptr(dev)                     # not the cached address of the dropped pair: a fresh pair ...
+            pair = hip.scratch.get("status", dev)
+            keep.append(pair)
+            assert pair.data_ptr() == ptr and pair.tolist() == [0, 0], "... whose words are 0"
+            assert hip.status_word(dev).data_ptr() == ptr
+        hip.release_stream(s)
+    assert len({p.data_ptr() for p in keep}) == len(streams)

@@ -158,8 +158,7 @@ def test_hip_forward_memory_is_the_declared_workspace(lib, dev):
     w = torch.rand(C, device=dev, generator=g) + 0.5
     need = lib.workspace_bytes(N, C)
     be = hip_backend()
-    for k in [k for k in be._ws if k[0] == "semloss"]:
-        del be._ws[k]
+    be.scratch.drop("semloss")
 
     def level():
         torch.cuda.synchronize()

@@ -197,6 +197,37 @@ def test_adamw_step_on_a_side_stream(dev, producer, side):
     assert busy, "the second step, on warm tables, waited for the device (or the producer was too short)"
 
 
+# ---- the scratch table itself --------------------------------------------------------------------------------------------------
+def test_scratch_table_is_per_stream(dev):
+    """`StreamScratch` on two side streams of one device: every name has storage of its own per stream, `release` of one
+    stream returns exactly the number of names it held and leaves the other stream's buffers and its status address alone.
+    No launch of ours."""
+    from pasco_amd._clib import StreamScratch
+    table = StreamScratch()
+    s0, s1 = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    assert s0.cuda_stream != s1.cuda_stream
+    held, ptr = {}, {}
+    for s in (s0, s1):
+        with torch.cuda.stream(s):
+            assert StreamScratch.key(torch.device("cuda")) == StreamScratch.key(dev) == (dev, s.cuda_stream)
+            held[s] = (table.bytes("ws", dev, 100, floor=1 << 20), table.bytes("attn", dev, 100), table.words("status", dev, 2))
+            ptr[s] = table.status_ptr(dev)
+            assert ptr[s] == held[s][2].data_ptr() and table.get("status", dev) is held[s][2]
+    assert [t.numel() for t in held[s0]] == [1 << 20, 100, 2]
+    for a, b in zip(held[s0], held[s1]):
+        assert a.data_ptr() != b.data_ptr() and a.device == b.device == dev
+    with torch.cuda.stream(s0):
+        table.words("keep_any", dev, 1)
+    assert table.held(s0) == {"ws", "attn", "status", "keep_any"} and table.held(s1) == {"ws", "attn", "status"}
+    assert table.held(torch.cuda.default_stream(dev)) == set()
+    assert table.release(s0) == 4 and table.held(s0) == set() and table.release(s0) == 0
+    assert table.held(s1) == {"ws", "attn", "status"}
+    with torch.cuda.stream(s1):
+        assert table.status_ptr(dev) == ptr[s1] and table.words("status", dev, 2) is held[s1][2]
+        assert table.bytes("ws", dev, 100, floor=1 << 20) is held[s1][0] and table.bytes("attn", dev, 100) is held[s1][1]
+    assert table.release(s1.cuda_stream) == 3 and table.held() == set(), "a raw handle: the streams of the current device"
+
+
 # ---- part 5: the harness can fail ----------------------------------------------------------------------------------------------
 def _make_fake(seed, dev):
     return {"x": torch.randn(4099, generator=sc._gen(seed)).to(dev)}
