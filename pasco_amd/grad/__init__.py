@@ -3,7 +3,8 @@ gradient and the bias gradient; of the dense <-> rows operators and local max po
 masked cross-attention (include/pasco_attngrad.h); the matcher and mask losses (include/pasco_match.h); and the semantic
 completion losses (include/pasco_semloss.h); and of training-mode batch normalisation over rows, local or synchronised
 (include/pasco_norm.h: `normlib` binds the `pn_*` entry points, `norm.batch_norm_rows` is the operator).  `host` restates them in torch (CPU tensors, the tensor's dtype), `lib` binds the
-`pg_*` entry points, `rowlib` the `pr_*` ones, `attnlib` the `pa_*` ones, `matchlib` the `pm_*` ones and `semlib` the `ps_*` ones;
+`pg_*` entry points, `rowlib` the `pr_*` ones, `poollib` the `pp_*` ones (include/pasco_pool.h: pooling, broadcast and the
+channel-wise convolution; `pool_ops` picks the binding or `host` for a tensor), `attnlib` the `pa_*` ones, `matchlib` the `pm_*` ones and `semlib` the `ps_*` ones;
 the functions here serve a tensor from the one its device calls for.  The autograd functions that use them are
 `pasco_amd.me.autograd`, `pasco_amd.grad.attention`, `pasco_amd.grad.criterion` and `pasco_amd.grad.semloss`.  The step that
 consumes the gradients is `optim.AdamW` (include/pasco_optim.h: `optimlib` binds the `po_*` entry points)."""
@@ -61,6 +62,31 @@ def maxpool_bwd(dy: torch.Tensor, arg: torch.Tensor, inv: torch.Tensor, n_in: in
         from .rowlib import rowgrad_lib
         return rowgrad_lib().maxpool_bwd(dy, arg, inv, n_in)
     return host.maxpool_bwd(dy, arg, inv, n_in)
+
+
+class _HostPool:
+    """`host.pool_*` under the method names of `poollib.PoolLib`."""
+    seg_reduce = staticmethod(host.pool_seg_reduce)
+    seg_max_bwd = staticmethod(host.pool_seg_max_bwd)
+    broadcast = staticmethod(host.pool_broadcast)
+    broadcast_mul_bwd = staticmethod(host.pool_broadcast_mul_bwd)
+    pool = staticmethod(host.pool_pool)
+    pool_bwd = staticmethod(host.pool_pool_bwd)
+    chconv_fwd = staticmethod(host.pool_chconv_fwd)
+    chconv_wgrad = staticmethod(host.pool_chconv_wgrad)
+
+
+_HOST_POOL = _HostPool()
+
+
+def pool_ops(t: torch.Tensor):
+    """What serves the include/pasco_pool.h operators for `t`: the `pp_*` binding on a GPU (fp32 only), `host` otherwise."""
+    if t.is_cuda:
+        if t.dtype != torch.float32:
+            raise TypeError(f"the pooling / broadcast / channel-wise kernels serve fp32 rows on the device, got {t.dtype}")
+        from .poollib import pool_lib
+        return pool_lib()
+    return _HOST_POOL
 
 
 def attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q: bool = True, need_k: bool = True, need_v: bool = True):

@@ -1,4 +1,4 @@
-"""Torch restatement of include/pasco_grad.h, include/pasco_rowgrad.h, include/pasco_attngrad.h and include/pasco_norm.h for CPU tensors: index
+"""Torch restatement of include/pasco_grad.h, include/pasco_rowgrad.h, include/pasco_pool.h, include/pasco_attngrad.h and include/pasco_norm.h for CPU tensors: index
 operations and matrix products in the tensor's dtype.  The
 CPU tests run on it and `pasco_amd.me.autograd` uses it where the features are not on a GPU.  Same results as the kernels up to
 the order of the fp32 sums.  The last section restates include/pasco_optim.h (`optim_*`): the optimiser step of
@@ -106,6 +106,136 @@ def maxpool_bwd(dy: torch.Tensor, arg: torch.Tensor, inv: torch.Tensor, n_in: in
         oc = o.clamp(0, n_out - 1)
         dx = dx + torch.where(have[:, None] & (arg[oc] == rows), dy[oc], torch.zeros_like(dx))
     return dx
+
+
+# ---- include/pasco_pool.h ---------------------------------------------------------------------------------------------------
+POOL_SUM, POOL_AVG, POOL_MAX = 0, 1, 2
+POOL_BC_ADD, POOL_BC_MUL, POOL_BC_CAT, POOL_BC_COPY = 0, 1, 2, 3
+
+
+def _batch_rows(coords: torch.Tensor, B: int):
+    """-> (in range bool [n], batch index int64 [n] clamped into [0, B))."""
+    b = coords[:, 0].long()
+    return (b >= 0) & (b < B), b.clamp(0, B - 1)
+
+
+def pool_seg_reduce(x: torch.Tensor, coords: torch.Tensor, B: int, mode: int):
+    """pp_seg_reduce in torch, in the dtype of `x`: x [n, c], coords int32 [n, 4] -> (out [B, c], count [B], arg int32 [B, c] |
+    None).  A batch index without rows gives a zero row; the max's arg is the first row whose value == the maximum, -1 for an
+    empty segment or a NaN maximum."""
+    n, c = x.shape
+    ok, b = _batch_rows(coords, B)
+    count = torch.zeros(B, dtype=x.dtype, device=x.device).index_add_(0, b[ok], torch.ones(int(ok.sum()), dtype=x.dtype, device=x.device))
+    if mode != POOL_MAX:
+        out = torch.zeros((B, c), dtype=x.dtype, device=x.device).index_add_(0, b[ok], x[ok])
+        if mode == POOL_AVG:
+            out = torch.where(count[:, None] > 0, out / count.clamp(min=1)[:, None], out)
+        return out, count, None
+    out = torch.zeros((B, c), dtype=x.dtype, device=x.device)
+    arg = torch.full((B, c), -1, dtype=torch.int32, device=x.device)
+    rows = torch.arange(n, device=x.device)
+    for s in range(B):
+        sel = rows[ok & (b == s)]
+        if sel.numel() == 0:
+            continue
+        seg = x[sel]
+        nan = torch.isnan(seg).any(dim=0)
+        m = torch.where(nan, torch.full_like(seg[0], float("nan")), torch.nan_to_num(seg, nan=float("-inf")).max(dim=0).values)
+        hit = seg == m                                        # nothing equals a NaN
+        first = torch.where(hit.any(dim=0), hit.to(torch.int64).argmax(dim=0), torch.zeros(c, dtype=torch.int64, device=x.device))
+        arg[s] = torch.where(hit.any(dim=0), sel[first], torch.full_like(first, -1)).to(torch.int32)
+        out[s] = torch.where(nan, m, seg.gather(0, first[None, :])[0])       # the first row's bits (+0 against -0)
+    return out, count, arg
+
+
+def pool_seg_max_bwd(dy: torch.Tensor, arg: torch.Tensor, n: int) -> torch.Tensor:
+    """pp_seg_max_bwd in torch: dy [B, c], arg int32 [B, c] -> dx [n, c], dy[b][ch] stored at row arg[b][ch]."""
+    B, c = dy.shape
+    dx = torch.zeros((n, c), dtype=dy.dtype, device=dy.device)
+    ok = (arg >= 0) & (arg < n)
+    ch = torch.arange(c, device=dy.device)[None, :].expand(B, c)
+    dx[arg.long()[ok], ch[ok]] = dy[ok]
+    return dx
+
+
+def pool_broadcast(x, g: torch.Tensor, coords: torch.Tensor, mode: int, cnt=None) -> torch.Tensor:
+    """pp_broadcast in torch: x [n, c] (None for copy), g [B, cg] -> x + v | x * v | cat(x, v) | v with v = g[b_i] (divided by
+    cnt[b_i] where `cnt` is given); a batch index outside [0, B) gives a zero output row."""
+    ok, b = _batch_rows(coords, g.shape[0])
+    v = g if cnt is None else torch.where(cnt[:, None] > 0, g / cnt.clamp(min=1)[:, None], torch.zeros_like(g))
+    v = v[b]
+    out = {POOL_BC_ADD: lambda: x + v, POOL_BC_MUL: lambda: x * v, POOL_BC_CAT: lambda: torch.cat([x, v], dim=1),
+           POOL_BC_COPY: lambda: v}[mode]()
+    return torch.where(ok[:, None], out, torch.zeros_like(out))
+
+
+def pool_broadcast_mul_bwd(dy, x, g, coords, need_x: bool = True, need_g: bool = True):
+    """pp_broadcast_mul_bwd in torch: -> (dx = dy * g[b_i] | None, dg[b] = sum dy * x | None)."""
+    ok, b = _batch_rows(coords, g.shape[0])
+    dx = torch.where(ok[:, None], dy * g[b], torch.zeros_like(dy)) if need_x else None
+    dg = torch.zeros_like(g).index_add_(0, b[ok], (dy * x)[ok]) if need_g else None
+    return dx, dg
+
+
+def _window_rows(table: torch.Tensor, k: int, n_src: int):
+    r = table[k].long()
+    return (r >= 0) & (r < n_src), r.clamp(0, max(n_src - 1, 0))
+
+
+def pool_pool(x: torch.Tensor, nbr: torch.Tensor, mode: int):
+    """pp_pool in torch: x [n_in, c], nbr int32 [K, n_out] -> (out [n_out, c], cnt [n_out]); terms added in ascending k; the
+    average divides by the number of PRESENT neighbours; an empty window gives a zero row."""
+    K, n_out = nbr.shape
+    n_in, c = x.shape
+    out = torch.zeros((n_out, c), dtype=x.dtype, device=x.device)
+    cnt = torch.zeros(n_out, dtype=x.dtype, device=x.device)
+    if n_in:
+        for k in range(K):
+            have, r = _window_rows(nbr, k, n_in)
+            out = out + torch.where(have[:, None], x[r], torch.zeros_like(out))
+            cnt = cnt + have.to(x.dtype)
+    if mode == POOL_AVG:
+        out = torch.where(cnt[:, None] > 0, out / cnt.clamp(min=1)[:, None], out)
+    return out, cnt
+
+
+def pool_pool_bwd(dy: torch.Tensor, cnt, inv: torch.Tensor, n_in: int, mode: int) -> torch.Tensor:
+    """pp_pool_bwd in torch: dy [n_out, c], cnt [n_out], inv int32 [K, n_in] -> dx [n_in, c], terms in ascending k, each
+    dy[o] * (1 / cnt[o]) for the average."""
+    n_out, c = dy.shape
+    dx = torch.zeros((n_in, c), dtype=dy.dtype, device=dy.device)
+    if n_out == 0 or n_in == 0:
+        return dx
+    if mode == POOL_AVG:
+        dy = torch.where(cnt[:, None] > 0, dy * (1.0 / cnt.clamp(min=1))[:, None], torch.zeros_like(dy))
+    for k in range(inv.shape[0]):
+        have, o = _window_rows(inv, k, n_out)
+        dx = dx + torch.where(have[:, None], dy[o], torch.zeros_like(dx))
+    return dx
+
+
+def pool_chconv_fwd(x: torch.Tensor, nbr: torch.Tensor, w: torch.Tensor, bias=None) -> torch.Tensor:
+    """pp_chconv_fwd in torch: out[o][ch] = sum_k x[nbr[k][o]][ch] * w[k][ch] (+ bias[ch]), terms in ascending k."""
+    K, n_out = nbr.shape
+    n_in, c = x.shape
+    out = torch.zeros((n_out, c), dtype=x.dtype, device=x.device)
+    if n_in:
+        for k in range(K):
+            have, r = _window_rows(nbr, k, n_in)
+            out = out + torch.where(have[:, None], x[r] * w[k], torch.zeros_like(out))
+    return out if bias is None else out + bias.reshape(1, c)
+
+
+def pool_chconv_wgrad(x: torch.Tensor, dy: torch.Tensor, nbr: torch.Tensor) -> torch.Tensor:
+    """pp_chconv_wgrad in torch: dw[k][ch] = sum_o x[nbr[k][o]][ch] * dy[o][ch]."""
+    K, n_out = nbr.shape
+    n_in, c = x.shape
+    dw = torch.zeros((K, c), dtype=x.dtype, device=x.device)
+    if n_in and n_out:
+        for k in range(K):
+            have, r = _window_rows(nbr, k, n_in)
+            dw[k] = torch.where(have[:, None], x[r] * dy, torch.zeros_like(dy)).sum(dim=0)
+    return dw
 
 
 # ---- include/pasco_attngrad.h -----------------------------------------------------------------------------------------------

@@ -16,6 +16,8 @@ from .modules import (MinkowskiModuleBase, MinkowskiConvolution, MinkowskiConvol
                       MinkowskiPruning, MinkowskiMaxPooling, MinkowskiGlobalPooling,
                       MinkowskiGlobalAvgPooling, MinkowskiBroadcastMultiplication,
                       MinkowskiChannelwiseConvolution, MinkowskiPoolingTranspose, MinkowskiAvgPooling,
+                      MinkowskiSumPooling, MinkowskiGlobalSumPooling, MinkowskiGlobalMaxPooling,
+                      MinkowskiBroadcast, MinkowskiBroadcastAddition, MinkowskiBroadcastConcatenation,
                       cat)
 
 

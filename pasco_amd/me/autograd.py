@@ -1,10 +1,11 @@
 """Autograd of the sparse convolution family: `MinkowskiConvolution` / `...Transpose` / `...GenerativeConvolutionTranspose`,
 `MinkowskiPruning` and the two-map `SparseTensor.__add__`; and of the operators between them: `SparseTensor.dense()`,
-`to_sparse()`, the duplicate-dropping `SparseTensor(features, coordinates)` and `MinkowskiMaxPooling`.
+`to_sparse()`, the duplicate-dropping `SparseTensor(features, coordinates)` and `MinkowskiMaxPooling`; and of the pooling,
+broadcast and channel-wise modules (include/pasco_pool.h).
 
 Each function's `forward` performs the very launches the module performs without autograd (the caller passes its own launch
 helper), so the forward values are the same bits in every mode; only the `grad_fn` is new.  The backward launches are
-include/pasco_grad.h and include/pasco_rowgrad.h on the device and `pasco_amd.grad.host` for CPU tensors.  Once differentiable:
+include/pasco_grad.h, include/pasco_rowgrad.h and include/pasco_pool.h on the device and `pasco_amd.grad.host` for CPU tensors.  Once differentiable:
 no double backward.
 
 Used only when autograd is enabled and an input requires grad (`modules._ConvBase.conv_rows`, `MinkowskiPruning.forward`,
@@ -163,3 +164,138 @@ class MaxPoolFunction(torch.autograd.Function):
         arg, nbr = ctx.saved_tensors
         inv = ctx.mgr.kernel_map_inverse(nbr, ctx.n_in) if ctx.mgr is not None else G.nbr_invert(nbr, ctx.n_in)
         return G.maxpool_bwd(dy.contiguous(), arg, inv, ctx.n_in), None, None, None
+
+
+# ---- include/pasco_pool.h: per-batch reductions, broadcast, local sum / average pooling, pooling transpose, channel-wise convolution
+class SegReduceFunction(torch.autograd.Function):
+    """`MinkowskiGlobal{Sum,Avg,Max}Pooling`: out [B, c] = the per-batch sum / average / maximum of the rows (`ops.seg_reduce`).
+    Backward: the sum copies dy[b_i] to every row, the average copies dy[b_i] / count[b_i], the maximum stores dy[b][ch] at the
+    one row arg[b][ch] (none for an empty segment or a NaN maximum)."""
+
+    @staticmethod
+    def forward(ctx, x, coords, B, mode):
+        x = x.contiguous()
+        ops = G.pool_ops(x)
+        out, count, arg = ops.seg_reduce(x, coords, B, mode)
+        ctx.save_for_backward(coords, count, arg)
+        ctx.ops, ctx.mode, ctx.n = ops, mode, x.shape[0]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        coords, count, arg = ctx.saved_tensors
+        dy = dy.contiguous()
+        if ctx.mode == G.host.POOL_MAX:
+            return ctx.ops.seg_max_bwd(dy, arg, ctx.n), None, None, None
+        cnt = count if ctx.mode == G.host.POOL_AVG else None
+        return ctx.ops.broadcast(None, dy, coords, G.host.POOL_BC_COPY, cnt), None, None, None
+
+
+class BroadcastFunction(torch.autograd.Function):
+    """`MinkowskiBroadcast{Addition,Multiplication,Concatenation}` and `MinkowskiBroadcast`: out[i] = x[i] (+, *, cat) g[b_i], or
+    g[b_i] alone (x is None).  Backward: the product's two gradients come out of one pass (`ops.broadcast_mul_bwd`); for the
+    others the rows' gradient is dy (or its leading columns) and the global tensor's is the per-batch sum of dy (or of its
+    trailing columns)."""
+
+    @staticmethod
+    def forward(ctx, x, g, coords, mode):
+        g = g.contiguous()
+        x = None if x is None else x.contiguous()
+        ops = G.pool_ops(g)
+        ctx.save_for_backward(coords, *((x, g) if mode == G.host.POOL_BC_MUL else ()))
+        ctx.ops, ctx.mode, ctx.B, ctx.c = ops, mode, g.shape[0], 0 if x is None else x.shape[1]
+        return ops.broadcast(x, g, coords, mode)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        coords = ctx.saved_tensors[0]
+        dy = dy.contiguous()
+        need_x, need_g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        d_x = d_g = None
+        if ctx.mode == G.host.POOL_BC_MUL:
+            _, x, g = ctx.saved_tensors
+            d_x, d_g = ctx.ops.broadcast_mul_bwd(dy, x, g, coords, need_x, need_g)
+        else:
+            if need_x:
+                d_x = dy[:, :ctx.c] if ctx.mode == G.host.POOL_BC_CAT else dy
+            if need_g:
+                d_g = ctx.ops.seg_reduce(dy[:, ctx.c:] if ctx.mode == G.host.POOL_BC_CAT else dy, coords, ctx.B, G.host.POOL_SUM)[0]
+        return d_x, d_g, None, None
+
+
+def gather_parents(x, parent, be):
+    """x[parent]: the backend's row gather on the device, the index operation for CPU tensors (any dtype)."""
+    return be.gather_rows(x, parent) if x.is_cuda else x[parent.long()]
+
+
+def _inverse(mgr, nbr, n_in):
+    return mgr.kernel_map_inverse(nbr, n_in) if mgr is not None else G.nbr_invert(nbr, n_in)
+
+
+class PoolFunction(torch.autograd.Function):
+    """`MinkowskiSumPooling` / `MinkowskiAvgPooling`: out[o] = the sum of the present neighbours (/ their number).  Backward over
+    the inverse table: dx[i] = sum_k dy[inv[k][i]] (* 1 / cnt[inv[k][i]])."""
+
+    @staticmethod
+    def forward(ctx, x, nbr, mode, mgr):
+        x = x.contiguous()
+        ops = G.pool_ops(x)
+        out, cnt = ops.pool(x, nbr, mode)
+        ctx.save_for_backward(nbr, cnt)
+        ctx.ops, ctx.mode, ctx.mgr, ctx.n_in = ops, mode, mgr, x.shape[0]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        nbr, cnt = ctx.saved_tensors
+        return ctx.ops.pool_bwd(dy.contiguous(), cnt, _inverse(ctx.mgr, nbr, ctx.n_in), ctx.n_in, ctx.mode), None, None, None
+
+
+class PoolTransposeFunction(torch.autograd.Function):
+    """`MinkowskiPoolingTranspose` at kernel == stride: out[child] = x[parent] (`be.gather_rows`; every child has one parent).
+    Backward: dx[parent] = the sum of its children's gradients, the local sum pooling over the inverse of the same table."""
+
+    @staticmethod
+    def forward(ctx, x, parent, nbr, be, mgr):
+        x = x.contiguous()
+        ctx.save_for_backward(nbr)
+        ctx.ops, ctx.mgr, ctx.n_in = G.pool_ops(x), mgr, x.shape[0]
+        return gather_parents(x, parent, be)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        (nbr,) = ctx.saved_tensors
+        return ctx.ops.pool(dy.contiguous(), _inverse(ctx.mgr, nbr, ctx.n_in), G.host.POOL_SUM)[0], None, None, None, None
+
+
+class ChannelwiseConvFunction(torch.autograd.Function):
+    """`MinkowskiChannelwiseConvolution`: out[o][ch] = sum_k x[nbr[k][o]][ch] * kernel[k][ch] (+ bias[ch]).  Backward: the input
+    gradient is the same operator over the inverse table with the same weights, the kernel's is `ops.chconv_wgrad`, the bias's
+    the column sum of dy."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, nbr, mgr):
+        x = x.contiguous()
+        ops = G.pool_ops(x)
+        w = kernel.detach().contiguous()
+        ctx.save_for_backward(x, w, nbr)
+        ctx.ops, ctx.mgr, ctx.has_bias = ops, mgr, bias is not None
+        return ops.chconv_fwd(x, nbr, w, None if bias is None else bias.detach().reshape(-1).contiguous())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, w, nbr = ctx.saved_tensors
+        dy = dy.contiguous()
+        d_x = d_w = d_b = None
+        if ctx.needs_input_grad[0]:
+            d_x = ctx.ops.chconv_fwd(dy, _inverse(ctx.mgr, nbr, x.shape[0]), w, None)
+        if ctx.needs_input_grad[1]:
+            d_w = ctx.ops.chconv_wgrad(x, dy, nbr)
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            d_b = G.colsum(dy).reshape(1, -1)
+        return d_x, d_w, d_b, None, None

@@ -419,6 +419,43 @@ class CoordinateManager:
             cache[key] = hit
         return hit[1]
 
+    def batch_count(self, key: CoordinateMapKey) -> int:
+        """Largest batch index of the map + 1 (1 for a map without rows): one host read per map, then cached.  A negative batch
+        index is refused."""
+        cache = self.__dict__.setdefault("_batch_cache", {})
+        hit = cache.get(key)
+        if hit is None:
+            m = self._maps[key]
+            lo, hi = (int(v) for v in torch.aminmax(m.coords[:, 0])) if m.n else (0, 0)
+            if lo < 0:
+                raise ValueError(f"batch index {lo} in {key}: batch indices are >= 0")
+            hit = cache[key] = hi + 1
+        return hit
+
+    def origin(self, in_key: CoordinateMapKey) -> Tuple[CoordinateMapKey, int]:
+        """-> (key of the origin map of `in_key`, B): one row per batch index 0 .. B - 1 in ascending order, coordinates
+        (b, 0, 0, 0), tensor stride [0, 0, 0] as upstream's global pooling gives; B = `batch_count(in_key)`, so a batch index
+        without rows still has its row.  Cached per input map."""
+        cache = self.__dict__.setdefault("_origin_cache", {})
+        hit = cache.get(in_key)
+        if hit is None:
+            B = self.batch_count(in_key)
+            coords = torch.zeros((B, 4), dtype=torch.int32)
+            coords[:, 0] = torch.arange(B, dtype=torch.int32)
+            hit = cache[in_key] = (self.insert_unique(coords.to(self._maps[in_key].coords.device), (0, 0, 0)), B)
+        return hit
+
+    def transpose_parents(self, nbr: torch.Tensor) -> torch.Tensor:
+        """int32 [n_child]: the one present entry per column of a kernel == stride transposed table of this manager (every child
+        has exactly one parent; the others are -1), built once per map."""
+        cache = self.__dict__.setdefault("_parent_cache", {})
+        key = nbr.data_ptr()
+        hit = cache.get(key)
+        if hit is None or hit[0] is not nbr:
+            hit = (nbr, nbr.max(dim=0).values.contiguous())
+            cache[key] = hit
+        return hit[1]
+
     def kernel_rowlist(self, nbr: torch.Tensor):
         """Row lists of a one-pair-per-row neighbour table of this manager (backend.rowlist_build), built once per map."""
         cache = self.__dict__.setdefault("_rl_cache", {})

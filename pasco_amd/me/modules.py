@@ -13,7 +13,11 @@ import torch
 import torch.nn as nn
 
 from . import backend as B
-from .autograd import ConvFunction, GatherRowsFunction, MaxPoolFunction, wants_grad
+from ..grad import pool_ops
+from ..grad.host import POOL_AVG, POOL_BC_ADD, POOL_BC_CAT, POOL_BC_COPY, POOL_BC_MUL, POOL_MAX, POOL_SUM
+from ..grad.poollib import PP_MAX_BATCH, PP_MAX_KVOL
+from .autograd import (BroadcastFunction, ChannelwiseConvFunction, ConvFunction, GatherRowsFunction, MaxPoolFunction, PoolFunction,
+                       PoolTransposeFunction, SegReduceFunction, gather_parents, wants_grad)
 from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple, apply_prologue, derived
 
 
@@ -393,37 +397,227 @@ class MinkowskiMaxPooling(MinkowskiModuleBase):
         return SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=mgr)
 
 
-# ---- names that only need to exist so that dead reference classes still define -------------------
-class _NotServed(MinkowskiModuleBase):
-    def __init__(self, *a, **kw):
+# ---- pooling, broadcast and channel-wise operators (include/pasco_pool.h) -------------------------------------------------------
+def _served_pool_kernel(name: str, kernel_size, stride, dilation, kernel_generator, dimension):
+    """The sizes of a pooling / channel-wise module as triples, refused outside the served range (that of `MinkowskiMaxPooling`
+    and `MinkowskiConvolution`: dimension 3, no kernel generator, a cubic kernel of at most PP_MAX_KVOL offsets, stride 1 with an
+    odd kernel or kernel == stride)."""
+    if dimension != 3:
+        raise ValueError(f"{name}: dimension=3 is the served case, got {dimension}")
+    if kernel_generator is not None:
+        raise ValueError(f"{name}: custom kernel generators are not served")
+    ks, st, dl = _triple(kernel_size), _triple(stride), _triple(dilation)
+    if not (ks[0] == ks[1] == ks[2] and st[0] == st[1] == st[2]):
+        raise ValueError(f"{name}: cubic kernels and isotropic strides are served, got kernel {list(ks)}, stride {list(st)}")
+    if _kvol(ks) > PP_MAX_KVOL:
+        raise ValueError(f"{name}: a window of {_kvol(ks)} offsets, at most {PP_MAX_KVOL} (PP_MAX_KVOL) are served")
+    if st == (1, 1, 1):
+        if ks[0] % 2 == 0:
+            raise ValueError(f"{name}: a stride-1 kernel must be odd, got {list(ks)}")
+    elif ks != st:
+        raise ValueError(f"{name}: a strided kernel is served for kernel == stride, got kernel {list(ks)}, stride {list(st)}")
+    return ks, st, dl
+
+
+def _pool_rows(x: SparseTensor) -> torch.Tensor:
+    """The features a pooling / broadcast module works on: a pending prologue is applied by reading `x.F`; on the device
+    anything but fp32 is refused."""
+    feats = x.F
+    if feats.is_cuda and feats.dtype != torch.float32:
+        raise TypeError(f"pasco_amd.me serves fp32 rows on the device, got {feats.dtype}")
+    return feats
+
+
+class _GlobalPooling(MinkowskiModuleBase):
+    """[n, c] rows -> one row per batch index 0 .. B - 1 (B = the largest batch index + 1) on the origin map of the input's
+    map: coordinates (b, 0, 0, 0), tensor stride [0, 0, 0].  A batch index without rows gives a zero row."""
+    MODE = POOL_AVG
+
+    def __init__(self, mode=None):          # upstream's PoolingMode argument: the served arithmetic does not depend on it
         super().__init__()
 
-    def forward(self, *a, **kw):
-        raise NotImplementedError(f"{type(self).__name__} is outside the served hot path (SURVEY.md 8(b))")
+    def forward(self, x: SparseTensor, coordinates=None) -> SparseTensor:
+        assert isinstance(x, SparseTensor)
+        assert coordinates is None, "explicit output coordinates are not served"
+        mgr = x.coordinate_manager
+        out_key, nb = mgr.origin(x.coordinate_map_key)
+        if nb > PP_MAX_BATCH:
+            raise ValueError(f"{type(self).__name__}: {nb} batch indices, at most {PP_MAX_BATCH} (PP_MAX_BATCH) are served")
+        feats = _pool_rows(x)
+        if wants_grad(feats):
+            out = SegReduceFunction.apply(feats, x.C, nb, self.MODE)
+        else:
+            out = pool_ops(feats).seg_reduce(feats.contiguous(), x.C, nb, self.MODE)[0]
+        return SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=mgr)
 
 
-class MinkowskiGlobalPooling(_NotServed):
-    pass
+class MinkowskiGlobalSumPooling(_GlobalPooling):
+    MODE = POOL_SUM
 
 
-class MinkowskiGlobalAvgPooling(_NotServed):
-    pass
+class MinkowskiGlobalAvgPooling(_GlobalPooling):
+    """reference: mink.py:27,40-42,53-75 (ASPP, SELayer); decoder_v3.py:46-74"""
+    MODE = POOL_AVG
 
 
-class MinkowskiBroadcastMultiplication(_NotServed):
-    pass
+class MinkowskiGlobalMaxPooling(_GlobalPooling):
+    MODE = POOL_MAX
 
 
-class MinkowskiChannelwiseConvolution(_NotServed):
-    pass
+class MinkowskiGlobalPooling(MinkowskiGlobalAvgPooling):
+    """Upstream's default global pooling: the average."""
 
 
-class MinkowskiPoolingTranspose(_NotServed):
-    pass
+class _Broadcast(MinkowskiModuleBase):
+    """forward(x, g): `g` holds one row per batch index (a global pooling's output); the result lives on x's map."""
+    MODE = POOL_BC_COPY
+
+    def forward(self, x: SparseTensor, g: SparseTensor) -> SparseTensor:
+        assert isinstance(x, SparseTensor) and isinstance(g, SparseTensor)
+        mgr = x.coordinate_manager
+        feats, glob = _pool_rows(x), _pool_rows(g)
+        nb = glob.shape[0]
+        if nb > PP_MAX_BATCH:
+            raise ValueError(f"{type(self).__name__}: {nb} batch indices, at most {PP_MAX_BATCH} (PP_MAX_BATCH) are served")
+        have = mgr.batch_count(x.coordinate_map_key)
+        if x.F.shape[0] and have > nb:
+            raise ValueError(f"{type(self).__name__}: the input has batch index {have - 1}, the global tensor has {nb} rows")
+        if self.MODE in (POOL_BC_ADD, POOL_BC_MUL) and glob.shape[1] != feats.shape[1]:
+            raise ValueError(f"{type(self).__name__}: {feats.shape[1]} channels against {glob.shape[1]} of the global tensor")
+        rows = None if self.MODE == POOL_BC_COPY else feats
+        if wants_grad(rows, glob):
+            out = BroadcastFunction.apply(rows, glob, x.C, self.MODE)
+        else:
+            out = pool_ops(glob).broadcast(None if rows is None else rows.contiguous(), glob.contiguous(), x.C, self.MODE)
+        return _same_map(x, out)
 
 
-class MinkowskiAvgPooling(_NotServed):
-    pass
+class MinkowskiBroadcast(_Broadcast):
+    MODE = POOL_BC_COPY
+
+
+class MinkowskiBroadcastAddition(_Broadcast):
+    MODE = POOL_BC_ADD
+
+
+class MinkowskiBroadcastMultiplication(_Broadcast):
+    """reference: mink.py:53-75 (SELayer); decoder_v3.py:46-74"""
+    MODE = POOL_BC_MUL
+
+
+class MinkowskiBroadcastConcatenation(_Broadcast):
+    MODE = POOL_BC_CAT
+
+
+class _LocalPooling(MinkowskiModuleBase):
+    """Sum / average over the maps and tables of `MinkowskiMaxPooling`.  The average divides by the number of neighbours that
+    EXIST (upstream's definition), not by the kernel volume."""
+    MODE = POOL_SUM
+
+    def __init__(self, kernel_size, stride=1, dilation=1, kernel_generator=None, dimension=None):
+        super().__init__()
+        self.kernel_size, self.stride, self.dilation = _served_pool_kernel(type(self).__name__, kernel_size, stride, dilation,
+                                                                           kernel_generator, dimension)
+
+    def forward(self, x: SparseTensor, coordinates=None) -> SparseTensor:
+        assert isinstance(x, SparseTensor)
+        assert coordinates is None, "explicit output coordinates are not served"
+        mgr = x.coordinate_manager
+        out_key = mgr.stride(x.coordinate_map_key, self.stride)
+        nbr = mgr.kernel_map(x.coordinate_map_key, out_key, self.kernel_size, self.dilation)
+        feats = _pool_rows(x)
+        if wants_grad(feats):
+            out = PoolFunction.apply(feats, nbr, self.MODE, mgr)
+        else:
+            out = pool_ops(feats).pool(feats.contiguous(), nbr, self.MODE)[0]
+        return SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=mgr)
+
+
+class MinkowskiSumPooling(_LocalPooling):
+    MODE = POOL_SUM
+
+
+class MinkowskiAvgPooling(_LocalPooling):
+    MODE = POOL_AVG
+
+
+class MinkowskiPoolingTranspose(MinkowskiModuleBase):
+    """reference: layers.py:264-276 (DepthwiseUpsample).  Served like the transposed convolutions: kernel 2, stride 2,
+    expand_coordinates=True, onto `mgr.expand(in_key, 2)`.  Every child then has exactly one parent and upstream's division by
+    the number of contributors is a division by one: out[child] = x[parent]."""
+
+    def __init__(self, kernel_size, stride, dilation=1, kernel_generator=None, expand_coordinates=False, dimension=None):
+        super().__init__()
+        if dimension != 3:
+            raise ValueError(f"MinkowskiPoolingTranspose: dimension=3 is the served case, got {dimension}")
+        if kernel_generator is not None:
+            raise ValueError("MinkowskiPoolingTranspose: custom kernel generators are not served")
+        if not expand_coordinates:
+            raise ValueError("MinkowskiPoolingTranspose: pooling transpose is served with expand_coordinates=True")
+        self.kernel_size, self.stride, self.dilation = _triple(kernel_size), _triple(stride), _triple(dilation)
+        if self.kernel_size != (2, 2, 2) or self.stride != (2, 2, 2):
+            raise ValueError(f"MinkowskiPoolingTranspose: pooling transpose is served for kernel 2 / stride 2, got kernel "
+                             f"{list(self.kernel_size)}, stride {list(self.stride)}")
+
+    def forward(self, x: SparseTensor, coordinates=None) -> SparseTensor:
+        assert isinstance(x, SparseTensor)
+        assert coordinates is None, "explicit output coordinates are not served"
+        mgr = x.coordinate_manager
+        in_key = x.coordinate_map_key
+        out_key = mgr.__dict__.setdefault("_expand_cache", {}).get(in_key)
+        if out_key is None:                     # one child map per parent map, as a strided map is cached per input map
+            out_key = mgr.__dict__["_expand_cache"][in_key] = mgr.expand(in_key, self.stride)
+        nbr = mgr.kernel_map(in_key, out_key, self.kernel_size, self.dilation, transposed=True)
+        parent = mgr.transpose_parents(nbr)
+        feats = _pool_rows(x)
+        if wants_grad(feats):
+            out = PoolTransposeFunction.apply(feats, parent, nbr, mgr.backend(), mgr)
+        else:
+            out = gather_parents(feats.contiguous(), parent, mgr.backend())
+        return SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=mgr)
+
+
+class MinkowskiChannelwiseConvolution(MinkowskiModuleBase):
+    """reference: layers.py:178-191 (DepthwiseSeparableConvMultiheads).  out[o][ch] = sum_k x[nbr[k][o]][ch] * kernel[k][ch]
+    (+ bias[ch]) over the maps of `MinkowskiConvolution`; parameters `kernel` [kvol, C] and `bias` [1, C] as upstream's."""
+
+    def __init__(self, in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, kernel_generator=None, dimension=None):
+        super().__init__()
+        self.kernel_size, self.stride, self.dilation = _served_pool_kernel("MinkowskiChannelwiseConvolution", kernel_size, stride,
+                                                                           dilation, kernel_generator, dimension)
+        self.in_channels = self.out_channels = in_channels
+        self.kernel_volume = _kvol(self.kernel_size)
+        self.dimension = dimension
+        self.kernel = nn.Parameter(torch.empty((self.kernel_volume, in_channels), dtype=torch.float32))
+        self.bias = nn.Parameter(torch.empty((1, in_channels), dtype=torch.float32)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():           # as `_ConvBase.reset_parameters`
+            stdv = 1.0 / math.sqrt(self.in_channels * self.kernel_volume)
+            self.kernel.uniform_(-stdv, stdv)
+            if self.bias is not None:
+                self.bias.uniform_(-stdv, stdv)
+
+    def forward(self, x: SparseTensor, coordinates=None) -> SparseTensor:
+        assert isinstance(x, SparseTensor)
+        assert coordinates is None, "explicit output coordinates are not served"
+        mgr = x.coordinate_manager
+        out_key = mgr.stride(x.coordinate_map_key, self.stride)
+        nbr = mgr.kernel_map(x.coordinate_map_key, out_key, self.kernel_size, self.dilation)
+        feats = _pool_rows(x)
+        if feats.shape[1] != self.in_channels:
+            raise ValueError(f"MinkowskiChannelwiseConvolution: {feats.shape[1]} channels, the kernel has {self.in_channels}")
+        if wants_grad(feats, self.kernel, self.bias):
+            out = ChannelwiseConvFunction.apply(feats, self.kernel, self.bias, nbr, mgr)
+        else:
+            bias = None if self.bias is None else self.bias.detach().reshape(-1).contiguous()
+            out = pool_ops(feats).chconv_fwd(feats.contiguous(), nbr, self.kernel.detach().contiguous(), bias)
+        return SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=mgr)
+
+    def extra_repr(self):
+        return (f"channels={self.in_channels}, kernel_size={list(self.kernel_size)}, stride={list(self.stride)}, "
+                f"dilation={list(self.dilation)}")
 
 
 def cat(*tensors):
