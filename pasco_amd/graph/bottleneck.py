@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import settings
 from ..me.backend import ACT_RELU, MAX_KVOL, backend_for
 from .fused import derived, fold_bn
 
@@ -117,6 +118,7 @@ class SPCDense3Dv2(nn.Module):
         n = rows.shape[0]
 
         from . import fused
+        presplit = settings.current().presplit
 
         in_splits = {}     # operand split of each intermediate, shared by the three branches that read it
 
@@ -130,8 +132,8 @@ class SPCDense3Dv2(nn.Module):
             split = in_split = None
             if fused.conv_precision() == "f16x3" and be.split_supported(w.shape[-2], w.shape[-1]):
                 # the row weight is itself an entry: a rebuilt one is another object, and this entry follows it
-                split = derived(self, "_split_" + name, (w,), fused._PRESPLIT, lambda: fused._split_of(w, be))
-                if fused._PRESPLIT:
+                split = derived(self, "_split_" + name, (w,), presplit, lambda: fused._split_of(w, be))
+                if presplit:
                     if id(x) not in in_splits:
                         in_splits[id(x)] = (x, be.split_rows(x))
                     in_split = in_splits[id(x)][1]

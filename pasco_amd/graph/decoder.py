@@ -17,14 +17,13 @@ masks by membership tests against given voxel sets.
 """
 from __future__ import annotations
 
-import os
 from collections import defaultdict
 from typing import Dict, List, Optional
 
 import torch
 import torch.nn as nn
 
-from .. import me as ME
+from .. import me as ME, settings
 from ..me.core import tensor_version
 from . import fused
 from .blocks import BasicGenerativeDeconvolutionBlock, ResidualBlock, SpatialDropout, run_sequential
@@ -72,7 +71,7 @@ def box_mask(mgr, coords: torch.Tensor, lo, hi) -> torch.Tensor:
             be = mgr.backend()
         except Exception:
             be = None
-        if be is not None and be.has("keep_mask") and os.environ.get("PASCO_KEEP_FUSED", "1") != "0":
+        if be is not None and be.has("keep_mask") and settings.current().keep_fused:
             lo_t, hi_t = _corner(lo, coords).reshape(3).contiguous(), _corner(hi, coords).reshape(3).contiguous()
             return be.keep_mask([], coords.contiguous(), lo_t, hi_t)
     return inside_bounds(coords, lo, hi)
@@ -177,10 +176,10 @@ class DecoderBlock(nn.Module):
         mgr = x.coordinate_manager
         conv = self.resize[1]
         c_in, c_out = conv.in_channels - 3, conv.out_channels
-        be = mgr.backend()
-        return bool(fused.fusion() and fused.conv_precision() == "f16x3" and fused._PRESPLIT and fused._kernel_device(x.F.device)
+        be, st = mgr.backend(), settings.current()
+        return bool(st.fusion and fused.conv_precision() == "f16x3" and st.presplit and fused._kernel_device(x.F.device)
                     and mgr.size(out_key) >= fused.MIN_ROWS_LINEAR and c_in % 32 == 0 and be.split_supported(c_in, c_out)
-                    and os.environ.get("PASCO_RESIZE_ABSORB", "1") != "0")
+                    and st.resize_absorb)
 
     def _resize_absorbed(self, x, out_key, nbr, out=None):
         """upsample -> [features | coords / ts] -> BN -> 1x1 conv (decoder_v3.py:103,133) without forming the C + 3 channel
@@ -280,7 +279,7 @@ class DecoderGenerativeSepConvV2(nn.Module):
             be = x.coordinate_manager.backend()
         except Exception:
             return None
-        return be if be.has("keep_mask") and os.environ.get("PASCO_KEEP_FUSED", "1") != "0" else None
+        return be if be.has("keep_mask") and settings.current().keep_fused else None
 
     def _keep_completion(self, x, scale, sem_logits, keep_override):
         srcs = [self._keep_sources(keep_override, scale, i, x, sem_logits[i] if sem_logits is not None else None)

@@ -18,6 +18,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from .. import settings
+
 
 def _host_staged(t: torch.Tensor, group=None) -> bool:
     """gloo moves host memory only (its device support is broadcast / all_reduce): device tensors of the other collectives are
@@ -174,8 +176,8 @@ def rank_cpu_set(local_rank: int, n_local: int, pci_bus_id: Optional[str] = None
 
 def pin_rank(local_rank: int, n_local: int, device_index: Optional[int] = None) -> List[int]:
     """Apply `rank_cpu_set` to the calling process (all its future threads inherit it) -> the CPUs chosen ([] when the
-    platform has no sched_setaffinity or PASCO_BENCH_PIN=0)."""
-    if os.environ.get("PASCO_BENCH_PIN", "1") == "0" or not hasattr(os, "sched_setaffinity"):
+    platform has no sched_setaffinity or `settings.bench_pin` is off, PASCO_BENCH_PIN=0)."""
+    if not settings.current().bench_pin or not hasattr(os, "sched_setaffinity"):
         return []
     bus = None
     try:
@@ -239,7 +241,7 @@ def subnet_parallel_forward(net, in_feat, global_min_coords, global_max_coords, 
     n_cls = net.n_classes + 1
     full = [None] * net.n_infers
     rounds = (net.n_infers + world - 1) // world
-    half = os.environ.get("PASCO_C4_EXCHANGE", "f32") == "f16"   # opt-in: mask logits travel as f16 (half the bytes, ~1e-3 rel)
+    half = settings.current().c4_exchange == "f16"   # opt-in: mask logits travel as f16 (half the bytes, ~1e-3 rel)
     stats = {"bytes_sent": 0, "bytes_padded": 0, "bytes_received": 0, "collectives": 0, "rounds": rounds,
              "payload": "f16" if half else "f32"}
     for r in range(rounds):                      # rank k owns subnets k, k + world, ...

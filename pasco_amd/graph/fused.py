@@ -11,24 +11,20 @@
 from __future__ import annotations
 
 import contextlib
-import os
 import threading
 from typing import Optional, Tuple
 
 import torch
 import torch.nn as nn
 
+from .. import settings
 from ..me import SparseTensor
 from ..me.core import derived, publish, tensor_version      # noqa: F401  (`derived`: the one cache every entry here goes through)
 from ..me.backend import ACT_LEAKY, ACT_NONE, ACT_RELU
 from ..me.modules import MinkowskiBatchNorm, _ConvBase
 
-_CONV_PRECISION = "f16x3"
-_PRESPLIT = True     # f16x3 operands pre-split once per tensor (mma_mode 2) instead of per gather (mode 1)
-_FUSION = True       # False: route (a) of INTEGRATION.md - every block as the reference's own module sequence
 MIN_ROWS_LINEAR = 16384    # tall-operand threshold above which linear layers run on the convolution kernel
 MIN_ROWS_WINDOWS = 16384   # 3x3x3 maps with at least this many rows get LDS-window tables (conv_win.hip)
-_WINDOWS_WIDE = os.environ.get("PASCO_CONV_WIN", "1") == "2"   # tables for 128-wide layers too (experiments)
 
 
 def _kernel_device(device) -> bool:
@@ -47,10 +43,8 @@ def set_conv_precision(mode: str) -> None:
     error against fp64 <= that of the fp32 MFMA path (tests/test_hip_f16x3.py), ~5x less matrix-pipe time;
     activations must stay inside the f16 range (checked on the device, `check_status`).
     "f32": every product on the exact fp32 MFMA."""
-    global _CONV_PRECISION, _PRESPLIT
-    assert mode in ("f32", "f16x3", "f16x3-inline")
-    _PRESPLIT = mode != "f16x3-inline"       # "-inline": the kernel converts at gather time (mode 1; for comparison)
-    _CONV_PRECISION = "f32" if mode == "f32" else "f16x3"
+    assert mode in ("f32", "f16x3", "f16x3-inline")      # "-inline": the kernel converts at gather time (mode 1; for comparison)
+    settings.replace(conv_precision="f32" if mode == "f32" else "f16x3", presplit=mode != "f16x3-inline")
 
 
 _TLS = threading.local()
@@ -58,7 +52,7 @@ _TLS = threading.local()
 
 def conv_precision() -> str:
     """The precision in force for the calling thread: a `precision_override` block, else the process-wide setting."""
-    return getattr(_TLS, "precision", None) or _CONV_PRECISION
+    return getattr(_TLS, "precision", None) or settings.current().conv_precision
 
 
 @contextlib.contextmanager
@@ -82,8 +76,8 @@ def optimistic() -> bool:
     transformer's outputs, the dense bottleneck's "no all-zero site".  Each saves one host synchronisation per use; each is
     exact whenever its flag stays down.  OFF unless the caller switched it on for the current thread
     (`optimistic_override(True)`) - only a caller that ends the step with `CBackend.check_status` and can redo it may do so:
-    `PascoNet.forward` does (PASCO_OPTIMISTIC=0 keeps it off); `UNet3DV2` / the modules used on their own take the checked
-    paths."""
+    `PascoNet.forward` does (`settings.optimistic`, PASCO_OPTIMISTIC=0, keeps it off); `UNet3DV2` / the modules used on their
+    own take the checked paths."""
     return bool(getattr(_TLS, "optimistic", False))
 
 
@@ -115,12 +109,11 @@ def set_fusion(on: bool) -> None:
     forward (exact fp32 products, bias only), a separate residual add - and the tall linear layers run as torch
     modules.  Same numbers as the fused graph to fp32 rounding; it exists so that the drop-in route has a GPU test
     and a benchmark row of its own."""
-    global _FUSION
-    _FUSION = bool(on)
+    settings.replace(fusion=bool(on))
 
 
 def fusion() -> bool:
-    return _FUSION
+    return settings.current().fusion
 
 
 def _act_rows(F: torch.Tensor, act: int, slope: float) -> torch.Tensor:
@@ -168,13 +161,13 @@ def _conv_unfused(x, mod, pro_bn, pro_act, epi_bn, epi_act, epi2_bn, residual, r
 
 
 def _split_of(w, be):
-    return be.split_weight_rows(w) if _PRESPLIT else be.split_weight_f16(w)
+    return be.split_weight_rows(w) if settings.current().presplit else be.split_weight_f16(w)
 
 
 def split_weight(mod, be):
     """Cached f16 split of a conv module's kernel: (w_split, unscale) for mode 2, (hi, lo, unscale) for mode 1."""
     w = mod.kernel
-    return derived(mod, "_ph_split", (w,), _PRESPLIT, lambda: _split_of(w, be))
+    return derived(mod, "_ph_split", (w,), settings.current().presplit, lambda: _split_of(w, be))
 
 
 def split_input(x: SparseTensor, be, ps, pb, pro_act, slope):
@@ -207,7 +200,8 @@ def gathered_split(x: SparseTensor, rows: torch.Tensor, out_key):
     mgr = x.coordinate_manager
     be = mgr.backend()
     c = x.F.shape[1]
-    if not (_FUSION and _PRESPLIT and conv_precision() == "f16x3" and be.split_supported(c, c) and x.F.shape[0] > 0):
+    st = settings.current()
+    if not (st.fusion and st.presplit and conv_precision() == "f16x3" and be.split_supported(c, c) and x.F.shape[0] > 0):
         return None
     op = split_input(x, be, None, None, ACT_NONE, 0.01)                     # [n, cpad / 32, 2, 32] f16
     n, cpad = op.shape[0], op.shape[1] * 32
@@ -218,7 +212,8 @@ def gathered_split(x: SparseTensor, rows: torch.Tensor, out_key):
 def split_rows_2d(x2d: torch.Tensor):
     """Pre-split operand of a tall [N, cin] matrix for several `linear_rows` calls on it (None when the split
     path does not apply)."""
-    if not (_FUSION and _kernel_device(x2d.device) and conv_precision() == "f16x3" and _PRESPLIT and x2d.shape[1] % 8 == 0):
+    st = settings.current()
+    if not (st.fusion and _kernel_device(x2d.device) and conv_precision() == "f16x3" and st.presplit and x2d.shape[1] % 8 == 0):
         return None
     from ..me.backend import backend_for
     return backend_for(x2d.device).split_rows(x2d.contiguous())
@@ -243,9 +238,9 @@ def linear_rows(x2d: Optional[torch.Tensor], weight: torch.Tensor, bias, cache_o
     cout, cin = weight.shape
     n = x2d.shape[0] if x2d is not None else in_split.shape[0]
     dev = x2d.device if x2d is not None else in_split.device
-    be = None
+    be, st = None, settings.current()
     min_rows = MIN_ROWS_LINEAR if min_rows is None else min_rows
-    if _FUSION and _kernel_device(dev) and n >= min_rows and conv_precision() == "f16x3":
+    if st.fusion and _kernel_device(dev) and n >= min_rows and conv_precision() == "f16x3":
         from ..me.backend import backend_for
         be = backend_for(dev)
         if not be.split_supported(cin, cout):
@@ -264,11 +259,11 @@ def linear_rows(x2d: Optional[torch.Tensor], weight: torch.Tensor, bias, cache_o
         wt = weight.detach().t().contiguous()                     # [cin, cout]
         return wt, _split_of(wt, be), bias.detach().contiguous() if bias is not None else None
 
-    wt, split, b = derived(cache_owner, "_ph_lin_" + cache_key, (weight, bias) if sources is None else sources, _PRESPLIT, build)
-    do_emit = emit and _PRESPLIT and cout % 32 == 0
+    wt, split, b = derived(cache_owner, "_ph_lin_" + cache_key, (weight, bias) if sources is None else sources, st.presplit, build)
+    do_emit = emit and st.presplit and cout % 32 == 0
     out = be.conv_fwd(None if (x2d is None) else x2d.contiguous(), wt, None, n,
                       xshape=(n, cin) if x2d is None else None, bias=b, split=split,
-                      in_split=in_split if _PRESPLIT else None,
+                      in_split=in_split if st.presplit else None,
                       residual=None if residual is None else residual.contiguous(),
                       emit_split=(None, None, ACT_NONE) if do_emit else None, want_out=want_out or not do_emit,
                       axis=axis, out=out)
@@ -299,8 +294,8 @@ def linear_bn_act(x2d: Optional[torch.Tensor], lin: nn.Linear, *, pro_bn=None, e
     cin, cout = lin.in_features, lin.out_features
     n = x2d.shape[0] if x2d is not None else in_split.shape[0]
     dev = x2d.device if x2d is not None else in_split.device
-    min_rows = MIN_ROWS_LINEAR if min_rows is None else min_rows
-    if not (_FUSION and _kernel_device(dev) and n >= min_rows):
+    min_rows, st = MIN_ROWS_LINEAR if min_rows is None else min_rows, settings.current()
+    if not (st.fusion and _kernel_device(dev) and n >= min_rows):
         assert x2d is not None
         y = x2d if pro_bn is None else pro_bn(x2d)
         y = lin(y)
@@ -321,12 +316,12 @@ def linear_bn_act(x2d: Optional[torch.Tensor], lin: nn.Linear, *, pro_bn=None, e
         split = _split_of(wt, be) if (precision == "f16x3" and be.split_supported(cin, cout)) else None
         return wt, split, lin.bias.detach().contiguous() if lin.bias is not None else None
 
-    wt, split, b = derived(lin, "_ph_lin_w", (w, lin.bias), (_PRESPLIT, precision), build)
-    do_emit = emit and split is not None and _PRESPLIT and cout % 32 == 0
-    assert x2d is not None or (split is not None and _PRESPLIT), "a pre-split operand needs the split path"
+    wt, split, b = derived(lin, "_ph_lin_w", (w, lin.bias), (st.presplit, precision), build)
+    do_emit = emit and split is not None and st.presplit and cout % 32 == 0
+    assert x2d is not None or (split is not None and st.presplit), "a pre-split operand needs the split path"
     out = be.conv_fwd(None if x2d is None else x2d.contiguous(), wt, None, n, xshape=(n, cin) if x2d is None else None,
                       bias=b, pro_scale=ps, pro_shift=pb, epi_scale=es, epi_shift=eb, epi_act=epi_act, split=split,
-                      in_split=in_split if (split is not None and _PRESPLIT) else None,
+                      in_split=in_split if (split is not None and st.presplit) else None,
                       emit_split=(None, None, ACT_NONE) if do_emit else None, want_out=not do_emit,
                       in_split_has_prologue=True, out_split=emit_into if do_emit else None, out=None if do_emit else out)
     if not emit:
@@ -439,8 +434,8 @@ def conv(x: SparseTensor, mod: _ConvBase, *, pro_bn=None, pro_act: int = ACT_NON
     lists grouped by offset instead of walking all offsets of every row.
     `out`: a contiguous fp32 [n_out, out_channels] buffer the result is written into (a slice of a batch the caller assembles:
     no copy afterwards)."""
-    mgr = x.coordinate_manager
-    if not _FUSION:
+    mgr, st = x.coordinate_manager, settings.current()
+    if not st.fusion:
         assert not isinstance(x, SplitRows)
         y = _conv_unfused(x, mod, pro_bn, pro_act, epi_bn, epi_act, epi2_bn, residual, res_act, slope, out_key, nbr)
         if out is not None:
@@ -470,7 +465,7 @@ def conv(x: SparseTensor, mod: _ConvBase, *, pro_bn=None, pro_act: int = ACT_NON
         xshape = None
         if conv_precision() == "f16x3" and be.split_supported(mod.in_channels, mod.out_channels):
             split = split_weight(mod, be)
-            if _PRESPLIT and n_out > 0:
+            if st.presplit and n_out > 0:
                 in_split = split_input(x, be, ps, pb, pro_act, slope)
     emit = None
     if emit_next is not None and in_split is not None and mod.out_channels % 32 == 0:
@@ -480,11 +475,11 @@ def conv(x: SparseTensor, mod: _ConvBase, *, pro_bn=None, pro_act: int = ACT_NON
     only = split_only and emit is not None and n_out > 0
     win = None
     if in_split is not None and nbr is not None and nbr.shape[0] == 27 and n_out >= MIN_ROWS_WINDOWS and \
-            be.device_type == "cuda" and (33 <= mod.out_channels <= 64 or _WINDOWS_WIDE):   # 64-wide tiles (measured)
+            be.device_type == "cuda" and (33 <= mod.out_channels <= 64 or st.conv_win_wide):   # 64-wide tiles (measured)
         win = mgr.kernel_windows(nbr)
     rowlist = None
     if one_pair and in_split is not None and nbr is not None and nbr.shape[0] <= 8 and n_out >= MIN_ROWS_LINEAR and \
-            be.device_type == "cuda" and os.environ.get("PASCO_CONV_RL", "1") != "0":
+            be.device_type == "cuda" and st.conv_rl:
         rowlist = mgr.kernel_rowlist(nbr)
     if out is not None:
         assert not only and out.is_contiguous() and tuple(out.shape) == (n_out, mod.out_channels) and out.dtype == torch.float32

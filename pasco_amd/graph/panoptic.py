@@ -26,7 +26,7 @@ from typing import List, Sequence
 import torch
 import torch.nn.functional as F
 
-from .. import me as ME
+from .. import me as ME, settings
 
 
 def to_dense(values: torch.Tensor, coords: torch.Tensor, scene_size, min_coords=None) -> torch.Tensor:
@@ -114,8 +114,7 @@ class PanopticResult(dict):
 
 
 def _device_backend(t: torch.Tensor):
-    import os
-    if os.environ.get("PASCO_PANOPTIC_KERNEL", "1") == "0":
+    if not settings.current().panoptic_kernel:
         return None
     from ..me.backend import backend_for
     try:

@@ -17,7 +17,6 @@ keep-mask stays sparse and level voxels look their parent block up in its hash m
 from __future__ import annotations
 
 import math
-import os
 import threading
 from typing import Optional
 
@@ -25,7 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import me as ME
+from .. import me as ME, settings
 from ..me.backend import backend_for
 from ..me.core import tensor_version
 from . import fused as fused_mod
@@ -515,7 +514,7 @@ class TransformerPredictorV2(nn.Module):
     def _query_step(self, layer: int, output, query_embed, want_operand: bool):
         """self-attention + FFN of decoder layer `layer` (layer < 0: none) followed by the query side of the heads.
         Everything here has the static shape [B, Q, D] and launches ~40 tiny kernels: on the GPU it is captured
-        once per (layer, shape) into a hipGraph and replayed (`PASCO_QUERY_GRAPH=0` or any capture failure ->
+        once per (layer, shape) into a hipGraph and replayed (`settings.query_graph` off or any capture failure ->
         eager)."""
         if layer >= 0:
             output = self.transformer_self_attention_layers[layer](output, query_pos=query_embed)
@@ -523,13 +522,13 @@ class TransformerPredictorV2(nn.Module):
         return (output,) + tuple(self.heads_query_side(output, want_operand))
 
     def query_graph_state(self) -> str:
-        """"graph" (query-side ops replayed from captured hipGraphs), "eager" (switched off: PASCO_QUERY_GRAPH=0, CPU,
+        """"graph" (query-side ops replayed from captured hipGraphs), "eager" (`settings.query_graph` off, PASCO_QUERY_GRAPH=0; CPU;
         training) or "eager (capture failed: ...)" - a capture failure is a performance cliff, so serving loops and
         bench.py report it instead of leaving a one-off warning behind."""
         broken = self.__dict__.get("_qgraph_broken", False)
         if broken:
             return f"eager (capture failed: {broken})"
-        if os.environ.get("PASCO_QUERY_GRAPH", "1") == "0" or not self.__dict__.get("_qgraphs"):
+        if not settings.current().query_graph or not self.__dict__.get("_qgraphs"):
             return "eager"
         return "graph"
 
@@ -555,7 +554,7 @@ class TransformerPredictorV2(nn.Module):
 
     def query_step(self, layer: int, output, query_embed, want_operand: bool, vers=None):
         if not output.is_cuda or self.training or torch.is_grad_enabled() or \
-                os.environ.get("PASCO_QUERY_GRAPH", "1") == "0" or self.__dict__.get("_qgraph_broken", False):
+                not settings.current().query_graph or self.__dict__.get("_qgraph_broken", False):
             return self._query_step(layer, output, query_embed, want_operand)
         graphs = self.__dict__.setdefault("_qgraphs", {})
         # a captured graph bakes in the ADDRESSES of every parameter it reads: the key carries version and storage
@@ -643,7 +642,7 @@ class TransformerPredictorV2(nn.Module):
         # (ph_bits_block_or) - no pooled map, no neighbour table, no dense-site map.  Exactly the reference's max-pool ->
         # dense -> index whenever no coordinate lies outside the subnet's [min, max] box (then the reference's dense
         # indexing wraps negative indices: the path below reproduces that); the test is made on the device and read once.
-        if be.has("bits_block_or") and os.environ.get("PASCO_MASK_BLOCK", "1") != "0":
+        if be.has("bits_block_or") and settings.current().mask_block:
             fine = mgr._maps[key1]
             # Host-side decision where the host knows the boxes (UNet3DV2.forward read them once): every REAL voxel of the
             # fine map and of the level lies inside its subnet's box (the panoptic branch prunes with exactly that test,
@@ -738,11 +737,11 @@ class TransformerPredictorV2(nn.Module):
 
         voxel_coord = xs[1][1]
         x1 = xs[1][0]
-        dev = x1.device
+        dev, st = x1.device, settings.current()
         # with the convolution kernel the position encoding is never materialised: it enters the projections' epilogues
         # as three table rows per voxel (ph_conv_desc.axis_table)
         use_tables = fused_mod.fusion() and fused_mod._kernel_device(dev) and fused_mod.conv_precision() == "f16x3" and \
-            os.environ.get("PASCO_PE_TABLE", "1") != "0"
+            st.pe_table
         tab = self.pe_layer.table(dev) if use_tables else None
         # voxel features of the mask heads: read only as the operand of `voxel_feat @ mask_embed^T`, so with the
         # split kernel the projection writes that operand directly (no fp32 copy, no separate split pass)
@@ -752,7 +751,7 @@ class TransformerPredictorV2(nn.Module):
         tables_ok = use_tables and c1.dtype == torch.int32 and x1.shape[0] * P >= fused_mod.MIN_ROWS_LINEAR
         # absorbed mask heads (heads_query_side): no [N, D] voxel features at all
         absorbed = None
-        if tables_ok and heads_split and x1.shape[-1] % 8 == 0 and os.environ.get("PASCO_HEAD_ABSORB", "1") != "0":
+        if tables_ok and heads_split and x1.shape[-1] % 8 == 0 and st.head_absorb:
             x1_split = split_rows_2d(x1.reshape(-1, x1.shape[-1]))
             if x1_split is not None:
                 absorbed = dict(x_split=x1_split, coords=c1.contiguous().view(B, P, 4), shape=(B, P, x1.shape[-1]))
@@ -801,8 +800,7 @@ class TransformerPredictorV2(nn.Module):
                 # the finest level's features are the mask heads' operand too: split once
                 x_split = absorbed["x_split"] if (absorbed is not None and srcs[i] is x1) else split_rows_2d(x2)
                 ci = ci.contiguous()
-            if tall and x_split is not None and be.attn_feat_supported(Qn, x2.shape[1]) and \
-                    os.environ.get("PASCO_ATTN_FEAT", "1") != "0":
+            if tall and x_split is not None and be.attn_feat_supported(Qn, x2.shape[1]) and st.attn_feat:
                 # attention straight on the level's feature operand: K and V (two [N, 384] operands written once and read
                 # once) and their projection launches do not exist (CrossAttentionLayer.composed_feat, ph_attn_cross_feat)
                 from ..me.backend import SPLIT_ACT_EXP2
@@ -819,7 +817,7 @@ class TransformerPredictorV2(nn.Module):
                                        axis=(cm["tk"], ci, self.pe_layer.TABLE_LO))
                 vv, v_op = linear_rows(x2, cm["wv"], cm["bv"], ca, "cv", in_split=x_split, emit=True, want_out=False,
                                        axis=(cm["tv"], ci, self.pe_layer.TABLE_LO))
-                if k_op is not None and v_op is not None and os.environ.get("PASCO_ATTN_SPLIT", "1") != "0":
+                if k_op is not None and v_op is not None and st.attn_split:
                     output = ca.attend(output, None, None, query_embed, (bits, any_), split=(k_op, v_op, N_i))
                 else:
                     kk = kk if kk is not None else _unsplit_rows(k_op, D)

@@ -14,8 +14,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import me as ME
-import os
+from .. import me as ME, settings
 
 from ..me.backend import F16RangeError, StatusError, backend_for
 from . import fused
@@ -98,7 +97,7 @@ class CylinderFeat(nn.Module):
             c0, c1 = m[1].in_features, m[1].out_features
             if fused.fusion() and fused._kernel_device(dev) and min(int(f.shape[0]) for f in fea) >= fused.MIN_ROWS_LINEAR:
                 from ..me.backend import backend_for as _bf
-                emit = fused.conv_precision() == "f16x3" and fused._PRESPLIT and c1 % 32 == 0 and _bf(dev).split_supported(c0, c1)
+                emit = fused.conv_precision() == "f16x3" and settings.current().presplit and c1 % 32 == 0 and _bf(dev).split_supported(c0, c1)
                 if emit:      # rows of the shared hidden operand
                     hs = torch.empty((total, c1 // 32, 2, 32), dtype=torch.float16, device=dev)
                 else:         # odd input width (283 = 27 + 256): exact-fp32 launches, rows of the shared fp32 result
@@ -276,7 +275,7 @@ class PascoNet(nn.Module):
     def prepare_input(self, in_feats: List[torch.Tensor], in_coords: List[torch.Tensor], fused_stage: bool = True) -> ME.SparseTensor:
         """`self.feat` + `ME.SparseTensor` + `Augmenter.merge` (net_panoptic_sparse.py:548-550).  On a device with a backend
         the voxel max and the merge are one sort-free pass over the points (`CBackend.pooled_merge`: no per-subnet voxel
-        tensor, no unique / sort, no dense detour); `fused_stage=False` or PASCO_INPUT_FUSED=0 runs the reference's
+        tensor, no unique / sort, no dense detour); `fused_stage=False` or `settings.input_fused` off runs the reference's
         sequence of steps (CylinderFeat.forward, SparseTensor, merge)."""
         x = self._prepare_input_fused(in_feats, in_coords) if fused_stage else None
         if x is None:
@@ -290,7 +289,7 @@ class PascoNet(nn.Module):
 
     def _prepare_input_fused(self, in_feats, in_coords):
         dev = in_feats[0].device
-        if self.training or os.environ.get("PASCO_INPUT_FUSED", "1") == "0" or len(in_feats) != self.n_infers or \
+        if self.training or not settings.current().input_fused or len(in_feats) != self.n_infers or \
                 not 1 <= self.n_infers <= 8:
             return None
         try:
@@ -324,7 +323,7 @@ class PascoNet(nn.Module):
                                   is_predict_panop=is_predict_panop, keep_override=keep_override, subnets=subnets)
         try:
             # this function ends the step with the status check and can redo it: the graph may take its optimistic shortcuts
-            with fused.optimistic_override(os.environ.get("PASCO_OPTIMISTIC", "1") != "0"):
+            with fused.optimistic_override(settings.current().optimistic):
                 ret = run()
             be.check_status(in_feat.device)     # flags of this stream's launches (f16 range, coordinate range, table clamp)
         except StatusError as err:

@@ -6,13 +6,13 @@ Parameter names/shapes follow upstream so reference checkpoints load: convolutio
 from __future__ import annotations
 
 import math
-import os
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import backend as B
+from .. import settings
 from ..grad import pool_ops
 from ..grad.host import POOL_AVG, POOL_BC_ADD, POOL_BC_CAT, POOL_BC_COPY, POOL_BC_MUL, POOL_MAX, POOL_SUM
 from ..grad.poollib import PP_MAX_BATCH, PP_MAX_KVOL
@@ -30,30 +30,20 @@ def _kvol(kernel_size) -> int:
     return k[0] * k[1] * k[2]
 
 
-_ME_CONV = os.environ.get("PASCO_ME_CONV", "guarded")
-_ME_DEFER = os.environ.get("PASCO_ME_DEFER", "1") != "0"      # eval-mode BatchNorm / ReLU recorded, applied by the next convolution
 ME_MIN_ROWS_WINDOWS = 16384     # 3x3x3 maps with at least this many rows get window tables (as pasco_amd.graph.fused does)
 
 
 def set_me_conv(mode: str) -> None:
     """"guarded" (default): the plain convolution modules run on the split-precision kernels with the exact fp32 kernel as a
     device-side fallback; "exact": the exact fp32 kernel only."""
-    global _ME_CONV
-    assert mode in ("guarded", "exact")
-    _ME_CONV = mode
-
-
-_ME_NORM = os.environ.get("PASCO_ME_NORM", "torch")
-assert _ME_NORM in ("torch", "device"), f"PASCO_ME_NORM={_ME_NORM!r}: 'torch' or 'device'"
+    settings.replace(me_conv=mode)
 
 
 def set_me_norm(mode: str) -> None:
     """"torch" (default): a training-mode `MinkowskiBatchNorm` is torch's batch_norm; "device": on fp32 GPU rows it is
     `pasco_amd.grad.norm.batch_norm_rows` (the pn_* kernels: fixed-order statistics).  `MinkowskiSyncBatchNorm`
     in a process group of more than one rank takes the pn_* route under either setting."""
-    global _ME_NORM
-    assert mode in ("torch", "device")
-    _ME_NORM = mode
+    settings.replace(me_norm=mode)
 
 
 class _ConvBase(MinkowskiModuleBase):
@@ -123,7 +113,7 @@ class _ConvBase(MinkowskiModuleBase):
         (`ph_conv_desc.exact_if`): it replaces the result exactly when it has to and costs an empty launch otherwise.  No
         host read, nothing for the caller to check - a maintainer who only swaps the import gets the fast kernels (round 5:
         the exact fp32 MFMA runs at 1 / 16 of the f16 rate and was ~85 % of the unfused route's time).
-        `PASCO_ME_CONV=exact` (or `set_me_conv("exact")`): the exact kernel only.
+        `settings.me_conv == "exact"` (`PASCO_ME_CONV=exact` or `set_me_conv("exact")`): the exact kernel only.
         `prologue` = (scale, shift, act, slope) of a deferred BatchNorm / activation in front (SparseTensor.deferred): applied
         to the gathered rows by the launch itself instead of by separate passes over the tensor.
         With autograd enabled and features, kernel or bias requiring grad the same launches run inside
@@ -150,7 +140,7 @@ class _ConvBase(MinkowskiModuleBase):
         if prologue is not None:
             ps, pb, pact, pslope = prologue
             pro = dict(pro_scale=ps, pro_shift=pb, pro_act=pact, slope=pslope)
-        if n_out == 0 or _ME_CONV != "guarded" or not be.split_supported(self.in_channels, self.out_channels) or exact:
+        if n_out == 0 or settings.current().me_conv != "guarded" or not be.split_supported(self.in_channels, self.out_channels) or exact:
             return be.conv_fwd(feats, kernel, nbr, n_out, bias=bias, **pro)
         # the same cache, under the same rule, as the fused graph's entries (`derived`: valid while the kernel is the same
         # object at the same version counter); a kernel made under torch.inference_mode() has no counter: split every call
@@ -235,10 +225,10 @@ class MinkowskiBatchNorm(nn.Module):
         return derived(self, "_ph_me_folded", (rm, rv, w, b, bufs.get("num_batches_tracked")), None, build, identity_suffices=False)
 
     def forward(self, x: SparseTensor) -> SparseTensor:
-        m = self.bn
-        if _ME_DEFER and not m.training and torch.is_grad_enabled():
+        m, defer = self.bn, settings.current().me_defer
+        if defer and not m.training and torch.is_grad_enabled():
             _warn_grad_mode_once()
-        if _ME_DEFER and not m.training and m.track_running_stats and m._buffers.get("running_mean") is not None \
+        if defer and not m.training and m.track_running_stats and m._buffers.get("running_mean") is not None \
                 and not torch.is_grad_enabled() and x._F.dtype == torch.float32:
             if x._pending is not None:
                 x.F                        # an activation is pending: it has to be applied before this affine
@@ -256,7 +246,7 @@ class MinkowskiBatchNorm(nn.Module):
 
     def _rows_route(self, feats: torch.Tensor):
         """-> (a training-mode forward goes through `batch_norm_rows`, its `gather`)."""
-        return _ME_NORM == "device" and feats.is_cuda and feats.dtype == torch.float32, None
+        return settings.current().me_norm == "device" and feats.is_cuda and feats.dtype == torch.float32, None
 
 
 class MinkowskiSyncBatchNorm(MinkowskiBatchNorm):
@@ -311,7 +301,7 @@ class _DeferredAct(_Elementwise):
     ACT = B.ACT_NONE
 
     def forward(self, x: SparseTensor) -> SparseTensor:
-        if _ME_DEFER and not torch.is_grad_enabled() and x._F.dtype == torch.float32:
+        if settings.current().me_defer and not torch.is_grad_enabled() and x._F.dtype == torch.float32:
             slope = float(getattr(self.module, "negative_slope", 0.01))
             if x._pending is not None and x._pending[2] == B.ACT_NONE:      # behind a deferred BatchNorm: one prologue
                 raw, (scale, shift, _, _) = x.take_prologue()

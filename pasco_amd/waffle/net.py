@@ -91,7 +91,7 @@ def linear(x: torch.Tensor, lin: _Lin, *, pro=None, act: int = ACT_NONE, epi_sca
     that and on the CPU - the rule `fused.linear_bn_act` follows, with the epilogue scale and the residual it does not take."""
     n = x.shape[0]
     min_rows = fused.MIN_ROWS_LINEAR if min_rows is None else min_rows
-    if not (fused._FUSION and fused._kernel_device(x.device) and n >= min_rows):
+    if not (fused.fusion() and fused._kernel_device(x.device) and n >= min_rows):
         y = x if pro is None else x * pro[0] + pro[1]
         y = torch.nn.functional.linear(y, lin.w, lin.b)
         y = torch.relu(y) if act == ACT_RELU else y

@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn as nn
 
+from pasco_amd import settings
 from pasco_amd.graph import fused
 from pasco_amd.graph.transformer import CrossAttentionLayer, PositionEmbeddingSineSparse, sine_position_encoding
 from pasco_amd.me import backend
@@ -98,9 +99,9 @@ def test_pos_aug_flags_a_coordinate_outside_the_table(split_checker):
         split_checker.check_status(torch.device("cpu"))
 
 
-def test_graph_takes_the_feature_operand_path(split_checker, monkeypatch):
+def test_graph_takes_the_feature_operand_path(split_checker):
     """PascoNet on the oracle with the split plumbing on: every cross-attention level runs on its feature operand, and the
-    result equals the K / V-operand path (PASCO_ATTN_FEAT=0)."""
+    result equals the K / V-operand path (`settings.attn_feat` off)."""
     from pasco_amd.graph import PascoNet
     from pasco_amd.graph.synth import TeacherKeep, make_scene
     old = fused.MIN_ROWS_LINEAR
@@ -129,8 +130,8 @@ def test_graph_takes_the_feature_operand_path(split_checker, monkeypatch):
         finally:
             del split_checker.attn_cross_feat
         assert calls["n"] == 3
-        monkeypatch.setenv("PASCO_ATTN_FEAT", "0")
-        ref = run()
+        with settings.override(attn_feat=False):
+            ref = run()
         for a, b in zip(got["panop_predictions"], ref["panop_predictions"]):
             assert torch.equal(a["voxel_logits"].C, b["voxel_logits"].C)
             assert torch.allclose(a["voxel_logits"].F, b["voxel_logits"].F, rtol=2e-4, atol=2e-4)

@@ -29,6 +29,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+from pasco_amd import settings
 from tests.launch_checker import LaunchChecker
 
 
@@ -145,10 +146,11 @@ def test_s10_mimo3_split_path_vs_exact_fp32(hip, s10_net):
           f"(floor 0.25 mean |y|) {worst['elementwise']:.2e}")
 
 
-@pytest.mark.parametrize("switch", ["PASCO_ATTN_FEAT", "PASCO_HEAD_ABSORB", "PASCO_ATTN_SPLIT", "PASCO_PE_TABLE", "PASCO_RESIZE_ABSORB", "PASCO_MASK_BLOCK"])
-def test_s10_transformer_restructurings_vs_plain_forms(hip, s10_net, switch, monkeypatch):
+@pytest.mark.parametrize("switch", ["attn_feat", "head_absorb", "attn_split", "pe_table", "resize_absorb", "mask_block"],
+                         ids=lambda field: "PASCO_" + field.upper())      # the ids the cases have always had
+def test_s10_transformer_restructurings_vs_plain_forms(hip, s10_net, switch):
     """The algebraic restructurings of the mask transformer at the benchmark size, each against the form it replaces
-    (the switch set to 0): mask heads absorbed into the level's features vs voxel features formed and multiplied
+    (the field of `pasco_amd.settings` switched off): mask heads absorbed into the level's features vs voxel features formed and multiplied
     (transformer_predictor_v2.py:143,150,202-218); attention on split K / V operands vs fp32 K / V; position encoding as
     table rows vs materialised; the decoder's `resize` (coordinate channels + BN + 1x1 convolution, decoder_v3.py:103,133)
     absorbed into a product on the up-sampled features plus table rows vs the concatenated form; attention-mask bits by block
@@ -161,9 +163,8 @@ def test_s10_transformer_restructurings_vs_plain_forms(hip, s10_net, switch, mon
             return net(x, scene.global_min_Cs, scene.global_max_Cs, scene.min_Cs, scene.max_Cs, keep_override=teacher)
 
     got = run()
-    monkeypatch.setenv(switch, "0")
-    exp = run()
-    monkeypatch.delenv(switch)
+    with settings.override(**{switch: False}):
+        exp = run()
     for i, (a, b) in enumerate(zip(got["panop_predictions"], exp["panop_predictions"])):
         assert torch.equal(a["voxel_logits"].C, b["voxel_logits"].C)
         for key in ("voxel_logits", "query_logits"):

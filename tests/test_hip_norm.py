@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import pasco_amd.me as ME
+from pasco_amd import settings
 from pasco_amd.grad import host
 from pasco_amd.me import modules as M
 from tests import norm_cases as nc
@@ -142,7 +143,7 @@ def device_norm():
 
 
 def test_default_module_forward_is_torchs_op(dev):
-    assert M._ME_NORM == "torch"
+    assert settings.current().me_norm == "torch"
     x, _, w, b, rm, rv = nc.inputs(65, 20, dev)
     coords = torch.cat([torch.zeros(65, 1, dtype=torch.int32), torch.arange(65, dtype=torch.int32)[:, None].expand(65, 3)], 1)
     for cls in (ME.MinkowskiBatchNorm, ME.MinkowskiSyncBatchNorm):

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import pasco_amd.me as ME
+from pasco_amd import settings
 from pasco_amd.me import modules as M
 
 
@@ -130,20 +131,15 @@ def _chain(device, defer, act="relu"):
     bn, conv = bn.to(device), conv.to(device)
     coords, feats = _scene(n=700, c=16, extent=(12, 12, 8), seed=2)
     x = ME.SparseTensor(feats.to(device), coords.to(device))
-    old = M._ME_DEFER
-    M._ME_DEFER = defer
-    try:
-        with torch.no_grad():
-            h = relu(bn(x))
-            pending = h._pending
-            y = conv(h)
-            # anything else that reads the values sees the computed tensor
-            hF = h.F.clone()
-            s = (h + h).F
-            p = ME.MinkowskiPruning()(h, feats[:, 0].to(device) > 0).F
-        return pending, hF.cpu(), y.F.cpu(), s.cpu(), p.cpu()
-    finally:
-        M._ME_DEFER = old
+    with settings.override(me_defer=defer), torch.no_grad():
+        h = relu(bn(x))
+        pending = h._pending
+        y = conv(h)
+        # anything else that reads the values sees the computed tensor
+        hF = h.F.clone()
+        s = (h + h).F
+        p = ME.MinkowskiPruning()(h, feats[:, 0].to(device) > 0).F
+    return pending, hF.cpu(), y.F.cpu(), s.cpu(), p.cpu()
 
 
 @pytest.mark.parametrize("act", ["relu", "leaky"])

@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 
 import pasco_amd.me as ME
-from pasco_amd.me import modules as M
+from pasco_amd import settings
 from tests import norm_cases as nc
 
 CPU = torch.device("cpu")
@@ -94,7 +94,7 @@ def test_virtual_ranks_at_128_channels():
 def test_default_module_forward_is_torchs_op(oracle_registered):
     """The default route is unchanged: a training-mode `MinkowskiBatchNorm` (and a `MinkowskiSyncBatchNorm` outside a process
     group) returns the bits of torch's batch_norm and moves the running statistics as it does."""
-    assert M._ME_NORM == "torch"
+    assert settings.current().me_norm == "torch"
     x, _, w, b, rm, rv = nc.inputs(65, 20, CPU)
     coords = torch.cat([torch.zeros(65, 1, dtype=torch.int32), torch.arange(65, dtype=torch.int32)[:, None].expand(65, 3)], 1)
     for cls in (ME.MinkowskiBatchNorm, ME.MinkowskiSyncBatchNorm):

@@ -4,6 +4,7 @@ status word reports bit 0; other status bits still raise; the status word is per
 import pytest
 import torch
 
+from pasco_amd import settings
 from pasco_amd.graph import PascoNet, fused
 from pasco_amd.graph.synth import TeacherKeep, make_scene
 from pasco_amd.me import backend
@@ -132,14 +133,13 @@ def _same(a, b):
 def test_optimistic_shortcuts_give_the_checked_paths_results_cpu(oracle_registered, monkeypatch):
     """`PascoNet.forward` takes its shortcuts without host reads (attention-mask block lookups, leading-rows selection, no
     all-zero bottleneck site) and validates them at the end of the step: whether they held (no fallback) or not (the step is
-    redone on the checked paths), the results are those of PASCO_OPTIMISTIC=0 bit for bit.  A forced violation must be seen."""
+    redone on the checked paths), the results are those of `settings.optimistic` off (PASCO_OPTIMISTIC=0) bit for bit.  A forced violation must be seen."""
     dev = torch.device("cpu")
     oracle_registered.status_word(dev).zero_()
     oracle_registered.optimistic_word(dev).zero_()
     net, scene = _net_scene()
-    monkeypatch.setenv("PASCO_OPTIMISTIC", "0")
-    ref = _run(net, scene, "cpu")
-    monkeypatch.delenv("PASCO_OPTIMISTIC")
+    with settings.override(optimistic=False):
+        ref = _run(net, scene, "cpu")
     net.optimistic_fallbacks = 0
     got = _run(net, scene, "cpu")
     _same(got, ref)

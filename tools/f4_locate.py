@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from tests.conftest import load_oracle
+from pasco_amd import settings
 from pasco_amd.me import backend
 from pasco_amd.graph import fused
 import tests.test_data_formats as T
@@ -37,12 +38,10 @@ fused.set_conv_precision("f32")
 _, got = T._frame_through_checkpoint("cuda")
 report("exact fp32 MFMA", got)
 fused.set_conv_precision("f16x3")
-for sw in ("PASCO_HEAD_ABSORB", "PASCO_PE_TABLE", "PASCO_RESIZE_ABSORB", "PASCO_QUERY_GRAPH", "PASCO_MASK_BLOCK", "PASCO_INPUT_FUSED",
-           "PASCO_KEEP_FUSED"):
-    os.environ[sw] = "0"
-    _, got = T._frame_through_checkpoint("cuda")
-    report(sw + "=0", got)
-    del os.environ[sw]
+for field in ("head_absorb", "pe_table", "resize_absorb", "query_graph", "mask_block", "input_fused", "keep_fused"):
+    with settings.override(**{field: False}):
+        _, got = T._frame_through_checkpoint("cuda")
+    report(field + " off", got)
 fused.set_fusion(False)
 _, got = T._frame_through_checkpoint("cuda")
 report("unfused ME modules", got)
