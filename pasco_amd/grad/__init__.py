@@ -4,7 +4,8 @@ masked cross-attention (include/pasco_attngrad.h); the matcher and mask losses (
 completion losses (include/pasco_semloss.h); and of training-mode batch normalisation over rows, local or synchronised
 (include/pasco_norm.h: `normlib` binds the `pn_*` entry points, `norm.batch_norm_rows` is the operator).  `host` restates them in torch (CPU tensors, the tensor's dtype), `lib` binds the
 `pg_*` entry points, `rowlib` the `pr_*` ones, `poollib` the `pp_*` ones (include/pasco_pool.h: pooling, broadcast and the
-channel-wise convolution; `pool_ops` picks the binding or `host` for a tensor), `attnlib` the `pa_*` ones, `matchlib` the `pm_*` ones and `semlib` the `ps_*` ones;
+channel-wise convolution; `pool_ops` picks the binding or `host` for a tensor), `fieldlib` the `pq_*` ones (include/pasco_field.h:
+point <-> voxel grouping, segment rows and interpolation; `field_ops`), `attnlib` the `pa_*` ones, `matchlib` the `pm_*` ones and `semlib` the `ps_*` ones;
 the functions here serve a tensor from the one its device calls for.  The autograd functions that use them are
 `pasco_amd.me.autograd`, `pasco_amd.grad.attention`, `pasco_amd.grad.criterion` and `pasco_amd.grad.semloss`.  The step that
 consumes the gradients is `optim.AdamW` (include/pasco_optim.h: `optimlib` binds the `po_*` entry points)."""
@@ -87,6 +88,30 @@ def pool_ops(t: torch.Tensor):
         from .poollib import pool_lib
         return pool_lib()
     return _HOST_POOL
+
+
+class _HostField:
+    """`host.field_*` under the method names of `fieldlib.FieldLib`."""
+    group = staticmethod(host.field_group)
+    seg_rows = staticmethod(host.field_seg_rows)
+    seg_max_bwd = staticmethod(host.field_seg_max_bwd)
+    gather_w = staticmethod(host.field_gather_w)
+    interp_map = staticmethod(host.field_interp_map)
+    interp_fwd = staticmethod(host.field_interp_fwd)
+
+
+_HOST_FIELD = _HostField()
+
+
+def field_ops(t: torch.Tensor, rows: bool = True):
+    """What serves the include/pasco_field.h operators for `t`: the `pq_*` binding on a GPU (`rows`: `t` holds feature rows, fp32
+    only), `host` otherwise."""
+    if t.is_cuda:
+        if rows and t.dtype != torch.float32:
+            raise TypeError(f"the point / voxel kernels (TensorField, slice, interpolation) serve fp32 rows on the device, got {t.dtype}")
+        from .fieldlib import field_lib
+        return field_lib()
+    return _HOST_FIELD
 
 
 def attn_cross_bwd(q, k, v, bits, any_, out, dout, need_q: bool = True, need_k: bool = True, need_v: bool = True):

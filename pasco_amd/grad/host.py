@@ -238,6 +238,145 @@ def pool_chconv_wgrad(x: torch.Tensor, dy: torch.Tensor, nbr: torch.Tensor) -> t
     return dw
 
 
+# ---- include/pasco_field.h --------------------------------------------------------------------------------------------------
+FIELD_SUM, FIELD_AVG, FIELD_MAX = 0, 1, 2
+FIELD_CORNERS = 8
+
+
+def field_group(keys: torch.Tensor, n_seg: int):
+    """pq_group in torch: keys int32 [n] (absent: negative or >= n_seg) -> (offsets int32 [n_seg + 1], perm int32 [n]), the stable
+    sort by key with the absent entries behind every segment."""
+    n_seg = int(n_seg)
+    k = keys.long()
+    k = torch.where((k < 0) | (k >= n_seg), torch.full_like(k, n_seg), k)
+    perm = torch.sort(k, stable=True).indices.to(torch.int32)
+    counts = torch.bincount(k, minlength=n_seg + 1)[:n_seg]
+    offsets = torch.zeros(n_seg + 1, dtype=torch.int64, device=keys.device)
+    offsets[1:] = torch.cumsum(counts, dim=0)
+    return offsets.to(torch.int32), perm
+
+
+def _field_members(offsets: torch.Tensor, perm: torch.Tensor, n_src: int, src_mod):
+    """-> (segment int64 [L], list entry int64 [L], source row int64 [L]) of the members that contribute, in list order."""
+    n_seg, n_list = offsets.numel() - 1, perm.numel()
+    src_mod = max(n_list, 1) if src_mod is None else int(src_mod)
+    o = offsets.long().clamp(0, n_list)
+    counts = (o[1:] - o[:-1]).clamp(min=0)
+    seg = torch.repeat_interleave(torch.arange(n_seg, device=perm.device), counts)
+    pos = o[:-1][seg] + (torch.arange(seg.numel(), device=perm.device) - (torch.cumsum(counts, 0) - counts)[seg])
+    j = perm.long()[pos]
+    row = j if src_mod >= n_list else j % src_mod
+    ok = (j >= 0) & (j < n_list) & (row < n_src)
+    return seg[ok], j[ok], row[ok], counts
+
+
+def field_seg_rows(x: torch.Tensor, offsets: torch.Tensor, perm: torch.Tensor, mode: int, w=None, src_mod=None):
+    """pq_seg_rows in torch, in the dtype of `x`: -> (out [n_seg, c], cnt [n_seg], arg int32 [n_seg, c] | None).  Member j of a
+    segment reads row j % src_mod (j itself by default) and the weight w[j]; an empty segment gives a zero row; the max's arg is
+    the first member, in list order, whose value == the maximum, -1 for an empty segment or a NaN maximum."""
+    n_src, c = x.shape
+    n_seg = offsets.numel() - 1
+    seg, j, row, counts = _field_members(offsets, perm, n_src, src_mod)
+    cnt = counts.to(x.dtype)
+    if mode != FIELD_MAX:
+        vals = x[row] if w is None else w.to(x.dtype)[j][:, None] * x[row]
+        out = torch.zeros((n_seg, c), dtype=x.dtype, device=x.device).index_add_(0, seg, vals)
+        if mode == FIELD_AVG:
+            out = torch.where(cnt[:, None] > 0, out / cnt.clamp(min=1)[:, None], out)
+        return out, cnt, None
+    assert w is None, "the maximum takes no weights"
+    vals = x[row]
+    L = vals.shape[0]
+    isn = torch.isnan(vals)
+    ninf = torch.full_like(vals, float("-inf"))
+    clean = torch.where(isn, ninf, vals)
+    segc = seg[:, None].expand(L, c)
+    nan_any = torch.zeros((n_seg, c), dtype=torch.int64, device=x.device).scatter_add_(0, segc, isn.long()) > 0
+    m = torch.full((n_seg, c), float("-inf"), dtype=x.dtype, device=x.device).scatter_reduce(0, segc, clean, "amax", include_self=True)
+    hit = (clean == m[seg]) & ~isn
+    pos = torch.arange(L, device=x.device)[:, None].expand(L, c)
+    first = torch.full((n_seg, c), L, dtype=torch.int64, device=x.device).scatter_reduce(
+        0, segc, torch.where(hit, pos, torch.full_like(pos, L)), "amin", include_self=True)
+    has = first < L
+    fc = first.clamp(max=max(L - 1, 0))
+    if L:
+        picked, pj = vals.gather(0, fc), j[fc]
+    else:
+        picked, pj = torch.zeros((n_seg, c), dtype=x.dtype, device=x.device), torch.zeros((n_seg, c), dtype=torch.int64, device=x.device)
+    out = torch.where(nan_any, torch.full_like(picked, float("nan")), torch.where(has, picked, torch.zeros_like(picked)))
+    arg = torch.where(has & ~nan_any, pj, torch.full_like(pj, -1)).to(torch.int32)
+    return out, cnt, arg
+
+
+def field_seg_max_bwd(dy: torch.Tensor, arg: torch.Tensor, n_src: int, src_mod=None) -> torch.Tensor:
+    """pq_seg_max_bwd in torch: dy [n_seg, c], arg int32 [n_seg, c] -> dx [n_src, c], dy[s][ch] stored at row arg[s][ch] % src_mod."""
+    n_seg, c = dy.shape
+    dx = torch.zeros((int(n_src), c), dtype=dy.dtype, device=dy.device)
+    a = arg.long()
+    row = a if src_mod is None else a % int(src_mod)
+    ok = (a >= 0) & (row < n_src)
+    ch = torch.arange(c, device=dy.device)[None, :].expand(n_seg, c)
+    dx[row[ok], ch[ok]] = dy[ok]
+    return dx
+
+
+def field_gather_w(x: torch.Tensor, idx: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
+    """pq_gather_w in torch: out[i] = x[idx[i]] * (1 / d[idx[i]]); a zero row where d == 0 or the index is outside [0, n_src)."""
+    n_src = x.shape[0]
+    i = idx.long()
+    ok = (i >= 0) & (i < n_src)
+    if n_src == 0:
+        return torch.zeros((i.numel(), x.shape[1]), dtype=x.dtype, device=x.device)
+    ic = i.clamp(0, n_src - 1)
+    dv = d.to(x.dtype)[ic]
+    ok = ok & (dv != 0)
+    scale = 1.0 / torch.where(ok, dv, torch.ones_like(dv))
+    return torch.where(ok[:, None], x[ic] * scale[:, None], torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+def field_interp_map(points: torch.Tensor, tkeys: torch.Tensor, tvals: torch.Tensor, ts: int):
+    """pq_interp_map in torch, in the dtype of `points` [m, 4] = (b, x, y, z): -> (rows int32 [8, m], weights [8, m]).  Corner
+    k = 4 ox + 2 oy + oz; weight (f_x f_y) f_z with f_d = 1 - |x_d - corner_d| / ts, not renormalised; a corner of weight 0 and
+    every corner of a point with a non-finite coordinate are absent.  The table is probed by the backend that serves the
+    tensors' device (`me.backend.backend_for`)."""
+    from ..me.backend import backend_for
+    m = points.shape[0]
+    ts = int(ts)
+    b, xyz = points[:, 0], points[:, 1:]
+    fine = torch.isfinite(points).all(dim=1) & (b >= 0) & (b < 1024) & (xyz.abs() < 262144).all(dim=1)
+    xyz = torch.where(fine[:, None], xyz, torch.zeros_like(xyz))
+    lower = torch.floor(xyz / ts) * ts
+    lower = torch.where(lower > xyz, lower - ts, lower)            # x * (1 / ts), torch's device quotient, can land on the next integer
+    lower = torch.where(lower + ts <= xyz, lower + ts, lower)      # (lower + ts is exact; x - lower would round)
+    f = torch.stack([((lower + ts) - xyz) / ts, (xyz - lower) / ts])          # [2, m, 3]: 1 - |x - corner| / ts, nothing cancels
+    bi = torch.where(fine, torch.floor(b), torch.zeros_like(b)).to(torch.int32)
+    rows = torch.full((FIELD_CORNERS, m), -1, dtype=torch.int32, device=points.device)
+    weights = torch.zeros((FIELD_CORNERS, m), dtype=points.dtype, device=points.device)
+    be = backend_for(points.device) if m else None
+    for k in range(FIELD_CORNERS):
+        o = ((k >> 2) & 1, (k >> 1) & 1, k & 1)
+        wk = (f[o[0], :, 0] * f[o[1], :, 1]) * f[o[2], :, 2]
+        wk = torch.where(fine, wk, torch.zeros_like(wk))
+        weights[k] = wk
+        if m:
+            corner = lower.to(torch.int32) + torch.tensor(o, dtype=torch.int32, device=points.device) * ts
+            found = be.map_find(torch.cat([bi[:, None], corner], dim=1).contiguous(), tkeys, tvals)
+            rows[k] = torch.where(fine & (wk != 0), found, torch.full_like(found, -1))
+    return rows, weights
+
+
+def field_interp_fwd(x: torch.Tensor, rows: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """pq_interp_fwd in torch: out[p] = sum over the present corners, in ascending k, of weights[k][p] * x[rows[k][p]]."""
+    n_in, c = x.shape
+    m = rows.shape[1]
+    out = torch.zeros((m, c), dtype=x.dtype, device=x.device)
+    if n_in:
+        for k in range(FIELD_CORNERS):
+            have, r = _window_rows(rows, k, n_in)
+            out = out + torch.where(have[:, None], weights[k].to(x.dtype)[:, None] * x[r], torch.zeros_like(out))
+    return out
+
+
 # ---- include/pasco_attngrad.h -----------------------------------------------------------------------------------------------
 def _attn_allow(bits, any_, B: int, N: int, Q: int, device):
     """bits int32 [B, N, 4] | None, any int32 [B, 4] | None -> allow bool [B, Q, N] | None by the forward's rules: bit q of a

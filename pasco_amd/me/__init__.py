@@ -7,8 +7,8 @@ from enum import Enum
 
 from . import utils  # noqa: F401
 from .backend import hip_backend, backend_for  # noqa: F401
-from .core import (CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, to_sparse,  # noqa: F401
-                   kernel_offsets)
+from .core import (CoordinateManager, CoordinateMapKey, SparseTensor, SparseTensorQuantizationMode,  # noqa: F401
+                   TensorField, to_sparse, kernel_offsets)
 from .modules import (MinkowskiModuleBase, MinkowskiConvolution, MinkowskiConvolutionTranspose,  # noqa: F401
                       MinkowskiGenerativeConvolutionTranspose, MinkowskiBatchNorm,
                       MinkowskiSyncBatchNorm, MinkowskiReLU, MinkowskiLeakyReLU, MinkowskiSigmoid,
@@ -18,14 +18,7 @@ from .modules import (MinkowskiModuleBase, MinkowskiConvolution, MinkowskiConvol
                       MinkowskiChannelwiseConvolution, MinkowskiPoolingTranspose, MinkowskiAvgPooling,
                       MinkowskiSumPooling, MinkowskiGlobalSumPooling, MinkowskiGlobalMaxPooling,
                       MinkowskiBroadcast, MinkowskiBroadcastAddition, MinkowskiBroadcastConcatenation,
-                      cat)
-
-
-class SparseTensorQuantizationMode(Enum):
-    RANDOM_SUBSAMPLE = 0
-    UNWEIGHTED_AVERAGE = 1
-    UNWEIGHTED_SUM = 2
-    NO_QUANTIZATION = 3
+                      MinkowskiInterpolation, cat)
 
 
 class MinkowskiAlgorithm(Enum):

@@ -1,7 +1,9 @@
 """Autograd of the sparse convolution family: `MinkowskiConvolution` / `...Transpose` / `...GenerativeConvolutionTranspose`,
 `MinkowskiPruning` and the two-map `SparseTensor.__add__`; and of the operators between them: `SparseTensor.dense()`,
 `to_sparse()`, the duplicate-dropping `SparseTensor(features, coordinates)` and `MinkowskiMaxPooling`; and of the pooling,
-broadcast and channel-wise modules (include/pasco_pool.h).
+broadcast and channel-wise modules (include/pasco_pool.h); and of the point <-> voxel operators (include/pasco_field.h):
+`TensorField.sparse()` and `SparseTensor(features, coordinates, quantization_mode=...)` under a sum / average / max mode,
+`SparseTensor.slice` and `MinkowskiInterpolation`.
 
 Each function's `forward` performs the very launches the module performs without autograd (the caller passes its own launch
 helper), so the forward values are the same bits in every mode; only the `grad_fn` is new.  The backward launches are
@@ -299,3 +301,75 @@ class ChannelwiseConvFunction(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[2]:
             d_b = G.colsum(dy).reshape(1, -1)
         return d_x, d_w, d_b, None, None
+
+
+# ---- include/pasco_field.h: quantisation of points to voxels, slice, interpolation
+class FieldReduceFunction(torch.autograd.Function):
+    """`TensorField.sparse()` under a sum / average / max mode: out [n_vox, c] = `ops.seg_rows` over the points of every voxel
+    (`offsets`, `perm`: the grouping of `inv`, the voxel row of every point).  Backward: the sum hands dy[inv[p]] to point p, the
+    average dy[inv[p]] * (1 / cnt[inv[p]]) (`ops.gather_w`), the maximum stores dy[v][ch] at the one point arg[v][ch].  A point
+    without a voxel gets a zero row.  No gradient goes to the coordinates."""
+
+    @staticmethod
+    def forward(ctx, x, offsets, perm, inv, mode, be):
+        x = x.contiguous()
+        ops = G.field_ops(x)
+        out, cnt, arg = ops.seg_rows(x, offsets, perm, mode)
+        ctx.save_for_backward(inv, cnt, arg)
+        ctx.ops, ctx.mode, ctx.n, ctx.be = ops, mode, x.shape[0], be
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        from .core import gather_or_zero
+        inv, cnt, arg = ctx.saved_tensors
+        dy = dy.contiguous()
+        if ctx.mode == G.host.FIELD_MAX:
+            d_x = ctx.ops.seg_max_bwd(dy, arg, ctx.n)
+        elif ctx.mode == G.host.FIELD_AVG:
+            d_x = ctx.ops.gather_w(dy, inv, cnt)
+        else:
+            d_x = gather_or_zero(dy, inv, ctx.be)
+        return d_x, None, None, None, None, None
+
+
+class SliceFunction(torch.autograd.Function):
+    """`SparseTensor.slice`: out[p] = x[inv[p]] (a zero row where inv[p] is -1).  Backward: dx[v] = the sum of the gradients of
+    the voxel's points in ascending point order (`ops.seg_rows`, sum) over the grouping `grouping(ops)` the manager caches."""
+
+    @staticmethod
+    def forward(ctx, x, inv, grouping, be):
+        from .core import gather_or_zero
+        x = x.contiguous()
+        ctx.ops, ctx.grouping = G.field_ops(x), grouping
+        return gather_or_zero(x, inv, be)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        offsets, perm = ctx.grouping(ctx.ops)
+        return ctx.ops.seg_rows(dy.contiguous(), offsets, perm, G.host.FIELD_SUM)[0], None, None, None
+
+
+class InterpolationFunction(torch.autograd.Function):
+    """`MinkowskiInterpolation`: out[p] = sum_k weights[k][p] * x[rows[k][p]] (`ops.interp_fwd`).  Backward: the [8, M] table
+    flattened is a list of 8 M entries keyed by input row; grouped (`ops.group`), the terms weights[j] * dy[j % M] of every input
+    row are added in ascending (k, p) (`ops.seg_rows` with w = weights, src_mod = M).  No gradient goes to the points."""
+
+    @staticmethod
+    def forward(ctx, x, rows, weights):
+        x = x.contiguous()
+        ops = G.field_ops(x)
+        ctx.save_for_backward(rows, weights)
+        ctx.ops, ctx.n_in = ops, x.shape[0]
+        return ops.interp_fwd(x, rows, weights)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        rows, weights = ctx.saved_tensors
+        m = rows.shape[1]
+        offsets, perm = ctx.ops.group(rows.reshape(-1), ctx.n_in)
+        d_x = ctx.ops.seg_rows(dy.contiguous(), offsets, perm, G.host.FIELD_SUM, w=weights.reshape(-1), src_mod=max(m, 1))[0]
+        return d_x, None, None

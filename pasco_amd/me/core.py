@@ -14,6 +14,7 @@ All device work goes through the C ABI (pasco_amd.me.backend); torch is only the
 from __future__ import annotations
 
 import itertools
+from enum import Enum
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -21,6 +22,81 @@ import torch
 from .backend import CBackend, backend_for
 
 _key_counter = itertools.count()
+
+
+class SparseTensorQuantizationMode(Enum):
+    """How points that share a voxel become one row (`TensorField.sparse`, `SparseTensor(features, coordinates)`)."""
+    RANDOM_SUBSAMPLE = 0               # the first point of the voxel, in input order
+    UNWEIGHTED_AVERAGE = 1
+    UNWEIGHTED_SUM = 2
+    NO_QUANTIZATION = 3                # refused where points share a voxel
+    MAX_POOL = 4
+    SPLAT_LINEAR_INTERPOLATION = 5     # not served
+
+
+_Q = SparseTensorQuantizationMode
+_Q_REDUCE = {_Q.UNWEIGHTED_SUM: 0, _Q.UNWEIGHTED_AVERAGE: 1, _Q.MAX_POOL: 2}        # grad.host FIELD_SUM / FIELD_AVG / FIELD_MAX
+
+
+def quantization_mode_of(mode) -> Optional[SparseTensorQuantizationMode]:
+    """The member `mode` names (a member, or an enum member of the same name from another module), None for None."""
+    if mode is None or isinstance(mode, _Q):
+        return mode
+    name = getattr(mode, "name", mode)
+    if isinstance(name, str) and name in _Q.__members__:
+        return _Q[name]
+    raise ValueError(f"quantization_mode: {mode!r} is not a SparseTensorQuantizationMode")
+
+
+def floor_points(coords: torch.Tensor, ts: int) -> torch.Tensor:
+    """Point coordinates [N, 4] = (b, x, y, z), float or int -> the int32 voxel coordinates (floor(b), floor(c / ts) * ts):
+    -0.5 lands in voxel -1."""
+    if coords.dtype.is_floating_point:
+        xyz = coords[:, 1:]
+        low = torch.floor(xyz / ts) * ts
+        low = torch.where(low > xyz, low - ts, low)              # x * (1 / ts), torch's device quotient, can land on the next integer
+        low = torch.where(low + ts <= xyz, low + ts, low)       # (low + ts is exact; x - low would round)
+        out = torch.cat([torch.floor(coords[:, :1]), low], dim=1)
+    else:
+        out = torch.cat([coords[:, :1], torch.div(coords[:, 1:], ts, rounding_mode="floor") * ts], dim=1)
+    return out.to(torch.int32).contiguous()
+
+
+def gather_or_zero(x: torch.Tensor, rows: torch.Tensor, be) -> torch.Tensor:
+    """x[rows] with a zero row where rows is -1: the backend's row gather on the device, index operations for CPU tensors (any
+    dtype)."""
+    if x.is_cuda:
+        return be.gather_rows(x, rows)
+    r = rows.long()
+    ok = (r >= 0) & (r < x.shape[0])
+    if x.shape[0] == 0:
+        return torch.zeros((r.numel(), x.shape[1]), dtype=x.dtype, device=x.device)
+    return torch.where(ok[:, None], x[r.clamp(0, x.shape[0] - 1)], torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+def quantize_rows(features: torch.Tensor, inv: torch.Tensor, n_vox: int, mode, be, grouping) -> torch.Tensor:
+    """The voxel rows [n_vox, C] of point rows [N, C] under a sum / average / max mode: `inv` int32 [N] is the voxel row of every
+    point (-1: none), `grouping(ops)` -> (offsets, perm) of `ops.group(inv, n_vox)` (include/pasco_field.h)."""
+    from ..grad import field_ops
+    from .autograd import FieldReduceFunction, wants_grad
+    ops = field_ops(features)
+    offsets, perm = grouping(ops)
+    if wants_grad(features):
+        return FieldReduceFunction.apply(features, offsets, perm, inv, _Q_REDUCE[mode], be)
+    return ops.seg_rows(features.contiguous(), offsets, perm, _Q_REDUCE[mode])[0]
+
+
+def _decompose(coords: torch.Tensor, feats: Optional[torch.Tensor]):
+    """-> (list of coordinates [n_b, 3], list of features [n_b, C]) per batch index 0 .. B - 1, rows in their order."""
+    b = torch.floor(coords[:, 0]) if coords.dtype.is_floating_point else coords[:, 0]
+    nb = int(b.max()) + 1 if coords.shape[0] else 0
+    cs, fs = [], []
+    for i in range(nb):
+        sel = b == i
+        cs.append(coords[sel][:, 1:])
+        if feats is not None:
+            fs.append(feats[sel])
+    return cs, fs
 
 
 def _triple(v) -> Tuple[int, int, int]:
@@ -185,6 +261,9 @@ class CoordinateManager:
         self._stride_cache: Dict[tuple, CoordinateMapKey] = {}
         self._kmap_cache: Dict[tuple, torch.Tensor] = {}
         self._origin: Dict[CoordinateMapKey, Tuple[CoordinateMapKey, torch.Tensor]] = {}
+        self._fields: Dict[CoordinateMapKey, torch.Tensor] = {}          # coordinate fields: the points as given, float or int
+        self._field_sparse: Dict[tuple, tuple] = {}                      # (field key, tensor stride) -> (map key, uniq_rows)
+        self._field_maps: Dict[tuple, dict] = {}                         # (field key, map key) -> {"inv", "group"}
 
     # -- basics ------------------------------------------------------------------------------------
     def backend(self) -> CBackend:
@@ -206,7 +285,56 @@ class CoordinateManager:
         for m in self._maps.values():
             if m.n:
                 bs.update(torch.unique(m.coords[:, 0]).tolist())
+        for c in self._fields.values():
+            if c.shape[0]:
+                bs.update(int(v) for v in torch.unique(torch.floor(c[:, 0].double())).tolist())
         return len(bs)
+
+    # -- coordinate fields (TensorField) -----------------------------------------------------------------
+    def insert_field(self, coords: torch.Tensor, tensor_stride=1) -> CoordinateMapKey:
+        """Register the points of a `TensorField` (kept as given) -> its coordinate field map key."""
+        if self.device is None:
+            self.device = coords.device
+        key = CoordinateMapKey(tensor_stride)
+        self._fields[key] = coords
+        return key
+
+    def get_field_coordinates(self, field_key: CoordinateMapKey) -> torch.Tensor:
+        return self._fields[field_key]
+
+    def field_to_sparse(self, field_key: CoordinateMapKey, tensor_stride=1):
+        """The voxel map of a field at `tensor_stride`: -> (map key, inv int32 [N] = the voxel row of every point, uniq_rows int32
+        [n_vox] = the first point of every voxel | None when no two points share a voxel).  The rows and their order are those
+        of `insert_and_map` on the floored coordinates (first occurrence); built once per (field, stride), with the one host read
+        of `map_insert`."""
+        ts = _triple(tensor_stride)
+        assert ts[0] == ts[1] == ts[2] and ts[0] >= 1, "isotropic tensor strides >= 1 only"
+        hit = self._field_sparse.get((field_key, ts))
+        if hit is None:
+            key, (inv, uniq_rows) = self.insert_and_map(floor_points(self._fields[field_key], ts[0]), ts)
+            self._field_maps[(field_key, key)] = {"inv": inv}
+            hit = self._field_sparse[(field_key, ts)] = (key, uniq_rows)
+        return hit[0], self._field_maps[(field_key, hit[0])]["inv"], hit[1]
+
+    def field_map(self, field_key: CoordinateMapKey, map_key: CoordinateMapKey) -> torch.Tensor:
+        """int32 [N]: the row of `map_key` every point of the field falls into, -1 where the map has no such voxel; computed once
+        per (field, map) and shared by `sparse`, every `slice` and their backwards."""
+        entry = self._field_maps.get((field_key, map_key))
+        if entry is None:
+            ts = map_key.tensor_stride
+            assert ts[0] == ts[1] == ts[2] and ts[0] >= 1, f"a field maps onto isotropic tensor strides >= 1, got {list(ts)}"
+            inv = self.find(map_key, floor_points(self._fields[field_key], ts[0]))
+            entry = self._field_maps[(field_key, map_key)] = {"inv": inv}
+        return entry["inv"]
+
+    def field_grouping(self, field_key: CoordinateMapKey, map_key: CoordinateMapKey, ops):
+        """(offsets int32 [n_vox + 1], perm int32 [N]): the points of every voxel of `map_key` in ascending point order
+        (include/pasco_field.h pq_group over `field_map`), built once per (field, map)."""
+        inv = self.field_map(field_key, map_key)
+        entry = self._field_maps[(field_key, map_key)]
+        if "group" not in entry:
+            entry["group"] = ops.group(inv.contiguous(), self.size(map_key))
+        return entry["group"]
 
     # -- map creation ------------------------------------------------------------------------------
     def insert_and_map(self, coords: torch.Tensor, tensor_stride=1):
@@ -500,7 +628,17 @@ class SparseTensor:
                 coordinate_manager = CoordinateManager(D=3, device=features.device)
             coordinate_map_key, (row2uniq, uniq_rows) = coordinate_manager.insert_and_map(
                 coordinates, tensor_stride)
-            if uniq_rows is not None:  # duplicates: keep the first occurrence (the dropped rows get a zero gradient)
+            mode = quantization_mode_of(quantization_mode)
+            if mode is _Q.SPLAT_LINEAR_INTERPOLATION:
+                raise NotImplementedError("SPLAT_LINEAR_INTERPOLATION is not served: quantise with an average, sum or max mode")
+            if mode is _Q.NO_QUANTIZATION and uniq_rows is not None:
+                raise ValueError(f"NO_QUANTIZATION: {features.shape[0] - uniq_rows.shape[0]} of {features.shape[0]} points share a "
+                                 "voxel with an earlier point")
+            if mode in _Q_REDUCE:          # every point of a voxel contributes (include/pasco_field.h)
+                n_vox = coordinate_manager.size(coordinate_map_key)
+                features = quantize_rows(features, row2uniq, n_vox, mode, coordinate_manager.backend(),
+                                         lambda ops: ops.group(row2uniq.contiguous(), n_vox))
+            elif uniq_rows is not None:  # duplicates: keep the first occurrence (the dropped rows get a zero gradient)
                 if torch.is_grad_enabled() and features.requires_grad:
                     from .autograd import GatherRowsFunction
                     features = GatherRowsFunction.apply(features, uniq_rows, coordinate_manager.backend())
@@ -685,9 +823,182 @@ class SparseTensor:
         c = self.C
         return c[c[:, 0] == batch_index][:, 1:]
 
+    @property
+    def decomposed_coordinates(self) -> List[torch.Tensor]:
+        return _decompose(self.C, None)[0]
 
-class TensorField:  # isinstance target only (pasco/models/dropout.py:23,47)
-    pass
+    @property
+    def decomposed_features(self) -> List[torch.Tensor]:
+        return _decompose(self.C, self.F)[1]
+
+    @property
+    def decomposed_coordinates_and_features(self):
+        return _decompose(self.C, self.F)
+
+    # -- back to the points (reference: the end of a MinkUNet-style segmenter) ----------------------
+    def slice(self, field: "TensorField") -> "TensorField":
+        """The field whose point p carries this tensor's row of the voxel p falls into: F[inverse_mapping].  A point whose voxel
+        is not in this tensor's map gets a zero row (ours).  A pending BatchNorm / ReLU is applied first."""
+        assert isinstance(field, TensorField), "slice takes the TensorField to return to"
+        mgr = self._manager
+        assert field.coordinate_manager is mgr, "slice needs a field of the same coordinate manager"
+        from ..grad import field_ops
+        from .autograd import SliceFunction, wants_grad
+        feats = self.F
+        field_ops(feats)                   # on the device anything but fp32 rows is refused
+        fkey, key, be = field.coordinate_field_map_key, self.coordinate_map_key, mgr.backend()
+        inv = mgr.field_map(fkey, key)
+        if wants_grad(feats):
+            out = SliceFunction.apply(feats, inv, lambda ops: mgr.field_grouping(fkey, key, ops), be)
+        else:
+            out = gather_or_zero(feats.contiguous(), inv, be)
+        return TensorField(out, coordinate_field_map_key=fkey, coordinate_manager=mgr, quantization_mode=field.quantization_mode)
+
+    def cat_slice(self, field: "TensorField") -> "TensorField":
+        """`slice(field)` with the field's own features behind it: [N, C + C_field]."""
+        out = torch.cat([self.slice(field).F, field.F], dim=1)
+        return TensorField(out, coordinate_field_map_key=field.coordinate_field_map_key, coordinate_manager=self._manager,
+                           quantization_mode=field.quantization_mode)
+
+
+class TensorField:
+    """Features on points with continuous coordinates (reference: maskpls/mink.py:453-468, models/dropout.py:23-59).  The
+    coordinates [N, 4] = (b, x, y, z), float or int, are kept as given and registered with the manager under
+    `coordinate_field_map_key`; `sparse()` quantises them to a `SparseTensor`, `SparseTensor.slice` brings voxel rows back."""
+
+    def __init__(self, features: torch.Tensor, coordinates: Optional[torch.Tensor] = None, tensor_stride=1,
+                 coordinate_field_map_key: Optional[CoordinateMapKey] = None,
+                 coordinate_manager: Optional[CoordinateManager] = None,
+                 quantization_mode=SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE, device=None, **_unused):
+        assert isinstance(features, torch.Tensor), "features must be a torch.Tensor"
+        assert features.dim() == 2, f"features must be [N, C], got {tuple(features.shape)}"
+        if device is not None:
+            features = features.to(device)
+        self.quantization_mode = quantization_mode_of(quantization_mode)
+        if coordinate_field_map_key is None:
+            assert coordinates is not None, "either coordinates or coordinate_field_map_key is required"
+            assert coordinates.dim() == 2 and coordinates.shape[1] == 4, "coordinates must be [N, 4] (b,x,y,z)"
+            assert coordinates.shape[0] == features.shape[0], "coordinates / features row mismatch"
+            coordinates = coordinates.to(features.device).contiguous()
+            if coordinates.dtype.is_floating_point and not bool(torch.isfinite(coordinates).all()):
+                raise ValueError("TensorField: the coordinates hold a NaN or an infinity")
+            if coordinate_manager is None:
+                coordinate_manager = CoordinateManager(D=3, device=features.device)
+            coordinate_field_map_key = coordinate_manager.insert_field(coordinates, tensor_stride)
+        else:
+            assert coordinate_manager is not None, "coordinate_field_map_key needs its coordinate_manager"
+            n = coordinate_manager.get_field_coordinates(coordinate_field_map_key).shape[0]
+            assert features.shape[0] == n, f"features have {features.shape[0]} rows, the field has {n} points"
+        self._F = features
+        self._manager = coordinate_manager
+        self.coordinate_field_map_key = coordinate_field_map_key
+
+    @property
+    def F(self) -> torch.Tensor:
+        return self._F
+
+    @property
+    def features(self) -> torch.Tensor:
+        return self._F
+
+    @property
+    def C(self) -> torch.Tensor:
+        return self._manager.get_field_coordinates(self.coordinate_field_map_key)
+
+    @property
+    def coordinates(self) -> torch.Tensor:
+        return self.C
+
+    @property
+    def coordinate_manager(self) -> CoordinateManager:
+        return self._manager
+
+    @property
+    def tensor_stride(self) -> List[int]:
+        return list(self.coordinate_field_map_key.tensor_stride)
+
+    @property
+    def shape(self):
+        return self._F.shape
+
+    @property
+    def device(self):
+        return self._F.device
+
+    @property
+    def dtype(self):
+        return self._F.dtype
+
+    @property
+    def D(self) -> int:
+        return 3
+
+    def __len__(self):
+        return self._F.shape[0]
+
+    def __repr__(self):
+        return (f"TensorField(N={self._F.shape[0]}, C={self._F.shape[1]}, quantization_mode={self.quantization_mode.name}, "
+                f"device={self.device})")
+
+    def _batch(self) -> torch.Tensor:
+        c = self.C
+        return torch.floor(c[:, 0]) if c.dtype.is_floating_point else c[:, 0]
+
+    def features_at(self, batch_index: int) -> torch.Tensor:
+        return self._F[self._batch() == batch_index]
+
+    def coordinates_at(self, batch_index: int) -> torch.Tensor:
+        return self.C[self._batch() == batch_index][:, 1:]
+
+    @property
+    def decomposed_coordinates(self) -> List[torch.Tensor]:
+        return _decompose(self.C, None)[0]
+
+    @property
+    def decomposed_features(self) -> List[torch.Tensor]:
+        return _decompose(self.C, self._F)[1]
+
+    @property
+    def decomposed_coordinates_and_features(self):
+        return _decompose(self.C, self._F)
+
+    def inverse_mapping(self, coordinate_map_key: CoordinateMapKey) -> torch.Tensor:
+        """int32 [N]: the row of `coordinate_map_key` each point falls into (-1: the map has no such voxel)."""
+        return self._manager.field_map(self.coordinate_field_map_key, coordinate_map_key)
+
+    def sparse(self, tensor_stride=1, coordinate_map_key: Optional[CoordinateMapKey] = None, quantization_mode=None) -> SparseTensor:
+        """The voxels of the points at `tensor_stride` (coordinates floor(c / ts) * ts, rows in order of their first point - what
+        `SparseTensor(features, floored coordinates)` gives), or the existing map `coordinate_map_key`; the points of a voxel
+        become its row under `quantization_mode` (default: the field's)."""
+        mode = self.quantization_mode if quantization_mode is None else quantization_mode_of(quantization_mode)
+        if mode is _Q.SPLAT_LINEAR_INTERPOLATION:
+            raise NotImplementedError("SPLAT_LINEAR_INTERPOLATION is not served: quantise with an average, sum or max mode")
+        mgr, fkey, feats = self._manager, self.coordinate_field_map_key, self._F
+        be = mgr.backend()
+        if coordinate_map_key is None:
+            key, inv, uniq_rows = mgr.field_to_sparse(fkey, tensor_stride)
+        else:
+            if mode not in _Q_REDUCE:
+                raise ValueError(f"sparse(coordinate_map_key=...): an average, sum or max mode is served onto an existing map, got {mode.name}")
+            key, inv, uniq_rows = coordinate_map_key, mgr.field_map(fkey, coordinate_map_key), None
+        if mode in _Q_REDUCE:
+            out = quantize_rows(feats, inv, mgr.size(key), mode, be, lambda ops: mgr.field_grouping(fkey, key, ops))
+        elif uniq_rows is None:            # every point has its own voxel: the rows as they are
+            out = feats
+        elif mode is _Q.NO_QUANTIZATION:
+            raise ValueError(f"NO_QUANTIZATION: {feats.shape[0] - uniq_rows.shape[0]} of {feats.shape[0]} points share a voxel with an "
+                             "earlier point")
+        else:                              # RANDOM_SUBSAMPLE: the first point of every voxel
+            from .autograd import GatherRowsFunction, wants_grad
+            if feats.is_cuda and feats.dtype != torch.float32:
+                raise TypeError(f"pasco_amd.me serves fp32 rows on the device, got {feats.dtype}")
+            if not feats.is_cuda and feats.element_size() != 4:       # the CPU checker's gather moves 4-byte elements only
+                out = feats[uniq_rows.long()]
+            elif wants_grad(feats):
+                out = GatherRowsFunction.apply(feats, uniq_rows, be)
+            else:
+                out = gather_or_zero(feats.contiguous(), uniq_rows, be)
+        return SparseTensor(out, coordinate_map_key=key, coordinate_manager=mgr)
 
 
 def to_sparse(x: torch.Tensor, format: Optional[str] = None, coordinates=None, device=None) -> SparseTensor:
@@ -709,14 +1020,15 @@ def to_sparse(x: torch.Tensor, format: Optional[str] = None, coordinates=None, d
 
 
 def batched_coordinates(coords: Sequence[torch.Tensor], dtype=torch.int32, device=None) -> torch.Tensor:
-    """Prepend the batch index: list of [N_i, 3] -> int32 [sum N_i, 4] (ME.utils.batched_coordinates;
+    """Prepend the batch index: list of [N_i, 3] -> `dtype` [sum N_i, 4] (ME.utils.batched_coordinates;
     transformer_predictor_v2.py:230,254, ensembler.py:54,152,178). Result lives on `device`
     (CPU by default, like upstream)."""
     out = []
     for b, c in enumerate(coords):
         if not isinstance(c, torch.Tensor):
             c = torch.as_tensor(c)
-        c = torch.floor(c) if c.dtype.is_floating_point else c
+        if c.dtype.is_floating_point and not dtype.is_floating_point:       # a float dtype keeps the points where they are (TensorField)
+            c = torch.floor(c)
         c = c.to(dtype)
         bcol = torch.full((c.shape[0], 1), b, dtype=dtype, device=c.device)
         out.append(torch.cat([bcol, c], dim=1))

@@ -13,11 +13,11 @@ import torch.nn as nn
 
 from . import backend as B
 from .. import settings
-from ..grad import pool_ops
+from ..grad import field_ops, pool_ops
 from ..grad.host import POOL_AVG, POOL_BC_ADD, POOL_BC_CAT, POOL_BC_COPY, POOL_BC_MUL, POOL_MAX, POOL_SUM
 from ..grad.poollib import PP_MAX_BATCH, PP_MAX_KVOL
-from .autograd import (BroadcastFunction, ChannelwiseConvFunction, ConvFunction, GatherRowsFunction, MaxPoolFunction, PoolFunction,
-                       PoolTransposeFunction, SegReduceFunction, gather_parents, wants_grad)
+from .autograd import (BroadcastFunction, ChannelwiseConvFunction, ConvFunction, GatherRowsFunction, InterpolationFunction,
+                       MaxPoolFunction, PoolFunction, PoolTransposeFunction, SegReduceFunction, gather_parents, wants_grad)
 from .core import CoordinateManager, CoordinateMapKey, SparseTensor, TensorField, _triple, apply_prologue, derived
 
 
@@ -608,6 +608,36 @@ class MinkowskiChannelwiseConvolution(MinkowskiModuleBase):
     def extra_repr(self):
         return (f"channels={self.in_channels}, kernel_size={list(self.kernel_size)}, stride={list(self.stride)}, "
                 f"dilation={list(self.dilation)}")
+
+
+class MinkowskiInterpolation(MinkowskiModuleBase):
+    """forward(input, tfield): the features of `input` at the points `tfield` [M, 4] = (b, x, y, z), linearly interpolated over the
+    eight voxels around each point -> [M, C] (a plain tensor, as upstream).  The weights are not renormalised over the corners
+    that exist: a point next to missing voxels gets a smaller row, a point with none a zero row.  `return_kernel_map` /
+    `return_weights` add the corner rows int32 [8, M] (-1: absent) / the weights [8, M] to the result."""
+
+    def __init__(self, return_kernel_map=False, return_weights=False):
+        super().__init__()
+        self.return_kernel_map, self.return_weights = bool(return_kernel_map), bool(return_weights)
+
+    def forward(self, input: SparseTensor, tfield: torch.Tensor):
+        assert isinstance(input, SparseTensor)
+        assert isinstance(tfield, torch.Tensor) and tfield.dim() == 2 and tfield.shape[1] == 4, "tfield must be [M, 4] (b,x,y,z)"
+        mgr, key = input.coordinate_manager, input.coordinate_map_key
+        ts = key.tensor_stride
+        if not (ts[0] == ts[1] == ts[2] and ts[0] >= 1):
+            raise ValueError(f"MinkowskiInterpolation: isotropic tensor strides >= 1 are served, got {list(ts)}")
+        feats = _pool_rows(input)
+        ops = field_ops(feats)
+        cmap = mgr._maps[key]
+        points = tfield.to(device=feats.device, dtype=feats.dtype).contiguous()
+        rows, weights = ops.interp_map(points, cmap.tkeys, cmap.tvals, ts[0])
+        if wants_grad(feats):
+            out = InterpolationFunction.apply(feats, rows, weights)
+        else:
+            out = ops.interp_fwd(feats.contiguous(), rows, weights)
+        extra = ((rows,) if self.return_kernel_map else ()) + ((weights,) if self.return_weights else ())
+        return (out,) + extra if extra else out
 
 
 def cat(*tensors):
