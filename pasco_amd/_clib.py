@@ -1,6 +1,6 @@
 """What every ctypes binding of libpascohip.so shares: setting the signatures, the ABI handshake, the error path, the stream
 handle, the per-stream scratch table and the process-wide instances.  `me.backend` (ph_*) uses `bind`, `_raw_stream` and
-`StreamScratch`; the side families (pa_*, pe_*, pf_*, pg_*, pl_*, pm_*, pn_*, po_*, pp_*, pq_*, pr_*, ps_*, pt_*, pv_*, pw_*) derive their
+`StreamScratch`; the side families (pa_*, pe_*, pf_*, pg_*, pk_*, pl_*, pm_*, pn_*, po_*, pp_*, pq_*, pr_*, ps_*, pt_*, pv_*, pw_*) derive their
 binding class from `FamilyLib` and keep only their table and wrappers."""
 from __future__ import annotations
 

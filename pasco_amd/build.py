@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libpascohip.so")
-SOURCES = ["coords.hip", "conv.hip", "conv_f16x3.hip", "conv_dma.hip", "conv_lin.hip", "conv_wide.hip", "conv_grid.hip", "conv_win.hip", "conv_wop.hip", "rows.hip", "attn.hip", "input.hip", "panop.hip", "eval.hip", "frame.hip", "label.hip", "view.hip", "waffle.hip", "grad.hip", "rowgrad.hip", "attn_grad.hip", "match.hip", "semloss.hip", "target.hip", "norm.hip", "optim.hip", "pool.hip", "field.hip"]
+SOURCES = ["coords.hip", "conv.hip", "conv_f16x3.hip", "conv_dma.hip", "conv_lin.hip", "conv_wide.hip", "conv_grid.hip", "conv_win.hip", "conv_wop.hip", "rows.hip", "attn.hip", "input.hip", "panop.hip", "eval.hip", "frame.hip", "label.hip", "view.hip", "waffle.hip", "grad.hip", "rowgrad.hip", "attn_grad.hip", "match.hip", "semloss.hip", "target.hip", "norm.hip", "optim.hip", "pool.hip", "field.hip", "knn.hip"]
 HEADERS = ["ph_common.h", "conv_h2_common.h", "conv_plan.h", "side_common.h", os.path.join("..", "..", "include", "pasco_hip.h"),
            os.path.join("..", "..", "include", "pasco_eval.h"),
            os.path.join("..", "..", "include", "pasco_frame.h"),
@@ -28,7 +28,8 @@ HEADERS = ["ph_common.h", "conv_h2_common.h", "conv_plan.h", "side_common.h", os
            os.path.join("..", "..", "include", "pasco_norm.h"),
            os.path.join("..", "..", "include", "pasco_optim.h"),
            os.path.join("..", "..", "include", "pasco_pool.h"),
-           os.path.join("..", "..", "include", "pasco_field.h")]
+           os.path.join("..", "..", "include", "pasco_field.h"),
+           os.path.join("..", "..", "include", "pasco_knn.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -1,4 +1,4 @@
-// Host plumbing shared by the side surfaces (attn_grad.hip, eval.hip, field.hip, frame.hip, grad.hip, label.hip, match.hip, norm.hip, optim.hip, pool.hip, rowgrad.hip, semloss.hip, target.hip, view.hip, waffle.hip): the error text behind a
+// Host plumbing shared by the side surfaces (attn_grad.hip, eval.hip, field.hip, frame.hip, grad.hip, knn.hip, label.hip, match.hip, norm.hip, optim.hip, pool.hip, rowgrad.hip, semloss.hip, target.hip, view.hip, waffle.hip): the error text behind a
 // family's `last_error`, the checks after a launch or a runtime call, and the two exports every family has.  Included after
 // the family's own header; independent of the core ABI (no ph_common.h, no pasco_hip.h).  Everything lives in an unnamed
 // namespace, so every translation unit has its OWN error buffer: one family never shows another family's text.

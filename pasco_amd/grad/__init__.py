@@ -5,7 +5,8 @@ completion losses (include/pasco_semloss.h); and of training-mode batch normalis
 (include/pasco_norm.h: `normlib` binds the `pn_*` entry points, `norm.batch_norm_rows` is the operator).  `host` restates them in torch (CPU tensors, the tensor's dtype), `lib` binds the
 `pg_*` entry points, `rowlib` the `pr_*` ones, `poollib` the `pp_*` ones (include/pasco_pool.h: pooling, broadcast and the
 channel-wise convolution; `pool_ops` picks the binding or `host` for a tensor), `fieldlib` the `pq_*` ones (include/pasco_field.h:
-point <-> voxel grouping, segment rows and interpolation; `field_ops`), `attnlib` the `pa_*` ones, `matchlib` the `pm_*` ones and `semlib` the `ps_*` ones;
+point <-> voxel grouping, segment rows and interpolation; `field_ops`), `knnlib` the `pk_*` ones (include/pasco_knn.h: the
+bipartite k-nearest-neighbour search, weights and gather behind `knn.knn_up`; `knn.knn_ops`), `attnlib` the `pa_*` ones, `matchlib` the `pm_*` ones and `semlib` the `ps_*` ones;
 the functions here serve a tensor from the one its device calls for.  The autograd functions that use them are
 `pasco_amd.me.autograd`, `pasco_amd.grad.attention`, `pasco_amd.grad.criterion` and `pasco_amd.grad.semloss`.  The step that
 consumes the gradients is `optim.AdamW` (include/pasco_optim.h: `optimlib` binds the `po_*` entry points)."""

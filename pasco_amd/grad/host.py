@@ -1,7 +1,8 @@
 """Torch restatement of include/pasco_grad.h, include/pasco_rowgrad.h, include/pasco_pool.h, include/pasco_attngrad.h and include/pasco_norm.h for CPU tensors: index
 operations and matrix products in the tensor's dtype.  The
 CPU tests run on it and `pasco_amd.me.autograd` uses it where the features are not on a GPU.  Same results as the kernels up to
-the order of the fp32 sums.  The last section restates include/pasco_optim.h (`optim_*`): the optimiser step of
+the order of the fp32 sums.  `knn_*` restates include/pasco_knn.h (the search by brute force under the header's ordering
+rule: the same indices, the same fp32 d2 and weights).  The last section restates include/pasco_optim.h (`optim_*`): the optimiser step of
 `pasco_amd.grad.optim.AdamW` on CPU parameters, the same bits as the kernels given the same sum of squares."""
 from __future__ import annotations
 
@@ -375,6 +376,74 @@ def field_interp_fwd(x: torch.Tensor, rows: torch.Tensor, weights: torch.Tensor)
             have, r = _window_rows(rows, k, n_in)
             out = out + torch.where(have[:, None], weights[k].to(x.dtype)[:, None] * x[r], torch.zeros_like(out))
     return out
+
+
+# ---- include/pasco_knn.h ----------------------------------------------------------------------------------------------------
+KNN_MAX_K = 16                  # PK_MAX_K
+KNN_PAIRS = 1 << 22             # (query, candidate) pairs of one chunk of the brute force
+
+
+def knn_search(cand: torch.Tensor, q: torch.Tensor, k: int):
+    """pk_knn in torch, in the dtype of `cand` [n, 3] / `q` [m, 3]: -> (idx int32 [k, m], d2 [k, m]), nearest first, by brute
+    force under the header's ordering rule: d2 = (dx*dx + dy*dy) + dz*dz with d = cand - q, a smaller d2 is nearer, equal d2 goes
+    to the lower candidate index (a stable sort along the candidates).  Fewer than k candidates leave idx = -1, d2 = +inf; a
+    query with a non-finite coordinate has all k absent."""
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"k = {k}: 1 .. {KNN_MAX_K} neighbours are served")
+    n, m = cand.shape[0], q.shape[0]
+    idx = torch.full((k, m), -1, dtype=torch.int32, device=q.device)
+    d2 = torch.full((k, m), float("inf"), dtype=cand.dtype, device=q.device)
+    kk = min(k, n)
+    if kk == 0 or m == 0:
+        return idx, d2
+    q = q.to(cand.dtype)
+    step = max(1, KNN_PAIRS // n)
+    for a in range(0, m, step):
+        qa = q[a:a + step]
+        d = cand[None, :, :3] - qa[:, None, :3]
+        dd = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        val, pos = torch.sort(dd, dim=1, stable=True)
+        fine = torch.isfinite(qa[:, :3]).all(dim=1)
+        idx[:kk, a:a + step] = torch.where(fine[None, :], pos[:, :kk].t().to(torch.int32), torch.full_like(idx[:kk, a:a + step], -1))
+        d2[:kk, a:a + step] = torch.where(fine[None, :], val[:, :kk].t(), torch.full_like(d2[:kk, a:a + step], float("inf")))
+    return idx, d2
+
+
+def knn_weights(d2: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """pk_weights in torch, in the dtype of `d2` [k, m]: r_j = 1 / (d2_j + 1e-8) over the present entries (idx >= 0), the norm
+    added in ascending j, w_j = r_j / norm; zero weights for an absent entry and where the norm is zero or not finite.  The
+    constant is the fp32 nearest 1e-8 for fp32 rows (the kernel's), 1e-8 itself otherwise."""
+    eps = torch.tensor(1e-8, dtype=d2.dtype, device=d2.device)
+    present = idx >= 0
+    r = torch.where(present, 1.0 / (torch.where(present, d2, torch.zeros_like(d2)) + eps), torch.zeros_like(d2))
+    norm = torch.zeros_like(d2[0]) if d2.shape[0] else None
+    for j in range(d2.shape[0]):
+        norm = norm + r[j]
+    if norm is None:
+        return torch.zeros_like(d2)
+    ok = present.any(dim=0) & (norm != 0) & torch.isfinite(norm)
+    return torch.where(present & ok[None, :], r / torch.where(ok, norm, torch.ones_like(norm))[None, :], torch.zeros_like(d2))
+
+
+def knn_interp(x: torch.Tensor, idx: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """pk_interp_fwd in torch: out[p] = the sum over the entries with idx[j][p] in [0, n), in ascending j, of w[j][p] * x[idx[j][p]]."""
+    n, c = x.shape
+    k, m = idx.shape
+    out = torch.zeros((m, c), dtype=x.dtype, device=x.device)
+    if n:
+        for j in range(k):
+            have, r = _window_rows(idx, j, n)
+            out = out + torch.where(have[:, None], w[j].to(x.dtype)[:, None] * x[r], torch.zeros_like(out))
+    return out
+
+
+def knn_interp_bwd(dy: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, n: int) -> torch.Tensor:
+    """The backward of `knn_interp` with respect to x: the flattened [k, m] table grouped by candidate row (`field_group`), the
+    terms w[j][p] * dy[p] of a row added in ascending (j, p) (`field_seg_rows`, src_mod = m)."""
+    m = idx.shape[1]
+    offsets, perm = field_group(idx.reshape(-1), int(n))
+    return field_seg_rows(dy, offsets, perm, FIELD_SUM, w=w.reshape(-1), src_mod=max(m, 1))[0]
 
 
 # ---- include/pasco_attngrad.h -----------------------------------------------------------------------------------------------

@@ -441,6 +441,25 @@ class CoordinateManager:
         out_coords = be.gather_rows(children, uniq_rows) if nu != children.shape[0] else children
         return self._register(out_coords, tkeys, tvals, ts_out)
 
+    def transposed_target(self, in_key: CoordinateMapKey, stride) -> CoordinateMapKey:
+        """The map a non-expanding transposed convolution of `in_key` lands on: the map `in_key` was strided from (`stride` and
+        `stride_chain` record it), when that parent's tensor stride is in_key's / `stride`.  The key returned IS the parent's
+        key - a decoder's `cat(up(x4), x3)` sees one map.  Nothing is registered, inserted or read from the device.  A map
+        without such a parent (made by insert, prune, union or expand) is refused."""
+        s = _triple(stride)
+        ts_in = in_key.tensor_stride
+        hit = self._origin.get(in_key)
+        if hit is not None and tuple(p * a for p, a in zip(hit[0].tensor_stride, s)) == tuple(ts_in):
+            return hit[0]
+        want = [t // a if a and t % a == 0 else None for t, a in zip(ts_in, s)]
+        remedy = "Pass the target as forward(x, coordinates=its key or tensor), or build the module with expand_coordinates=True"
+        if hit is not None:
+            raise ValueError(f"{in_key} was strided from a map of tensor stride {list(hit[0].tensor_stride)}, a stride-{list(s)} "
+                             f"transposed convolution lands on tensor stride {want}: the recorded parent is no target.  {remedy}")
+        raise ValueError(f"{in_key} was not strided by {list(s)} from a map of this manager (tensor stride {want}): no target for a "
+                         "transposed convolution onto an existing map is recorded for a map made by insert, prune, union or "
+                         f"expand.  {remedy}")
+
     def expand_pruned(self, in_key: CoordinateMapKey, stride, keep_of) -> CoordinateMapKey:
         """`expand` followed by `prune(keep_of(children))` as ONE map event: the children of distinct parents are distinct
         (parents are multiples of their tensor stride), so the full child map - a hash build, a dedup compaction and a host

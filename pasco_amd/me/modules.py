@@ -77,16 +77,29 @@ class _ConvBase(MinkowskiModuleBase):
                 self.bias.uniform_(-stdv, stdv)
 
     # out key + neighbour table for an input tensor
-    def _maps(self, x: SparseTensor):
+    def _maps(self, x: SparseTensor, coordinates=None):
         mgr = x.coordinate_manager
         in_key = x.coordinate_map_key
+        assert coordinates is None or self.is_transpose, "explicit output coordinates are not served"
         if self.use_mm:
+            assert coordinates is None, "explicit output coordinates are not served"
             return in_key, None
-        if self.is_transpose:
-            assert self.expand_coordinates, "transposed convolution is served with expand_coordinates=True"
+        if self.is_transpose and self.expand_coordinates:
+            if coordinates is not None:
+                raise ValueError("coordinates= names the existing map a transposed convolution lands on; with "
+                                 "expand_coordinates=True the module generates its own output map")
             assert self.kernel_size == (2, 2, 2) and self.stride == (2, 2, 2), \
                 "generative transposed convolution is served for kernel 2 / stride 2"
             out_key = mgr.expand(in_key, self.stride)
+            nbr = mgr.kernel_map(in_key, out_key, self.kernel_size, self.dilation, transposed=True)
+        elif self.is_transpose:
+            if not (self.kernel_size == self.stride == (2, 2, 2)):
+                raise ValueError(f"a transposed convolution onto an existing map (expand_coordinates=False) is served for "
+                                 f"kernel_size == stride == 2, got kernel {list(self.kernel_size)}, stride {list(self.stride)}: "
+                                 f"kernel != stride is not served")
+            out_key = self._target(x, coordinates)
+            # a child at parent + o_k * ts_out uses kernel[k], as the generative route; a target row without a parent has an
+            # all-absent column (a zero row + bias), a parent without a child in the target appears in no column
             nbr = mgr.kernel_map(in_key, out_key, self.kernel_size, self.dilation, transposed=True)
         else:
             if self.stride != (1, 1, 1):
@@ -95,10 +108,31 @@ class _ConvBase(MinkowskiModuleBase):
             nbr = mgr.kernel_map(in_key, out_key, self.kernel_size, self.dilation, transposed=False)
         return out_key, nbr
 
+    def _target(self, x: SparseTensor, coordinates) -> CoordinateMapKey:
+        """The existing map a non-expanding transposed convolution writes: `coordinates` (a key of x's manager or a SparseTensor
+        on it, at tensor stride in / stride) where given, else the map x's map was strided from."""
+        mgr, in_key = x.coordinate_manager, x.coordinate_map_key
+        if coordinates is None:
+            return mgr.transposed_target(in_key, self.stride)
+        key = coordinates
+        if isinstance(coordinates, SparseTensor):
+            if coordinates.coordinate_manager is not mgr:
+                raise ValueError("coordinates=: the target tensor belongs to another coordinate manager than the input")
+            key = coordinates.coordinate_map_key
+        elif torch.is_tensor(coordinates):
+            raise ValueError("coordinates=: a coordinate tensor is not served, pass the CoordinateMapKey of a map of the input's "
+                             "manager or a SparseTensor on it")
+        if not isinstance(key, CoordinateMapKey) or key not in mgr._maps:
+            raise ValueError(f"coordinates=: {key!r} is no coordinate map of the input's manager (a key of another manager?)")
+        want = tuple(t // a if t % a == 0 else -1 for t, a in zip(in_key.tensor_stride, self.stride))
+        if tuple(key.tensor_stride) != want:
+            raise ValueError(f"coordinates=: the target has tensor stride {list(key.tensor_stride)}, a stride-{list(self.stride)} "
+                             f"transposed convolution of tensor stride {list(in_key.tensor_stride)} lands on {list(want)}")
+        return key
+
     def forward(self, x: SparseTensor, coordinates=None) -> SparseTensor:
         assert isinstance(x, SparseTensor)
-        assert coordinates is None, "explicit output coordinates are not served"
-        out_key, nbr = self._maps(x)
+        out_key, nbr = self._maps(x, coordinates)
         mgr = x.coordinate_manager
         raw, pending = x.take_prologue()
         if pending is not None and wants_grad(raw, self.kernel, self.bias):
@@ -166,7 +200,10 @@ class MinkowskiConvolution(_ConvBase):
 
 
 class MinkowskiConvolutionTranspose(_ConvBase):
-    """reference: mink.py:524-527 (kernel 2, stride 2, expand_coordinates=True)"""
+    """reference: mink.py:524-527 (kernel 2, stride 2, expand_coordinates=True) and mink.py:537-543 (kernel 2, stride 2 onto the
+    encoder's map: without expand_coordinates the output lands on the map the input's map was strided from, or on the map
+    `forward(x, coordinates=key | tensor on it)` names; out[child] = x[parent] @ kernel[k] + bias for the child at
+    parent + o_k * ts_out, the generative module's convention)"""
     is_transpose = True
 
     def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False,
